@@ -8,15 +8,23 @@ of B=128 sentences per GPU, src_len=tgt_len=50, driven through
 ``TensorFlowManager.execute`` exactly as the reference's training loop does.
 ``value`` = target tokens (non-pad target positions incl. </s>) per second over
 all GPUs.  The timed loop rotates through 8 DISTINCT batches that are resident in
-HBM when the timed region starts (never the same batch twice in a row); the same
-loop with batches assembled on the host and uploaded inside the step
-(``ms_per_step_fresh``: pre-indexed int32 ids; ``ms_per_step_strings``: token
-strings, the reference's feeding model) is reported next to it.
+HBM when the timed region starts (never the same batch twice in a row).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line (rank 0): the headline
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``), the workload, the loss of the
+last step, the data-parallel exchange (N > 1) and ``roofline_train`` (the timed step against the fp32 matrix peak,
+from the same timing).  ``--dump-outputs DIR`` writes what the last timed step returned, its losses, as
+DIR/<name>.npy (``dump_outputs``).
+
+``--full`` adds to the same line, measured after the headline's timed steps:
+  ``beam5_*``, ``greedy_*``  beam-5 and greedy decoding of the headline model;
+  ``ms_per_step_fresh``, ``ms_per_step_strings``  the timed loop with batches assembled on the host and uploaded
+                     inside the step (pre-indexed int32 ids; token strings, the reference's feeding model);
+  ``other_scaling``  the strong split next to the weak one (N > 1);
   ``roofline``       the fused Bahdanau attention step (nm_attn_fwd = ONE launch of attn_whole_fast<13>:
                      score + softmax + mask-renorm + context of a decoding step), HBM-bound, timed live
                      with HIP events on its stream: ``achieved`` / ``frac`` = 32 back-to-back launches
@@ -37,6 +45,7 @@ import argparse
 import ctypes
 import json
 import os
+import re
 import sys
 import time
 
@@ -81,6 +90,11 @@ def parse():
     ap.add_argument("--no-feed-legs", action="store_true", help="skip the fresh / strings feeding legs")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the legs of BASELINE configs[3] (captioning) and configs[4] (Transformer)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure decoding, the host-fed step, the attention roofline, the "
+                         "other configurations and the CPU baseline (the options above shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (its losses) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -563,64 +577,24 @@ def bf16x3_costing_leg(args, dev, lib):
             "speedup_over_exact_f32": t32 / t3}
 
 
-def main():
-    args = parse()
-    from neuralmonkey_amd import _lib, distributed, ops, synthetic
+def dump_outputs(path, res):
+    """What a caller of the timed training step receives from its last call (``TensorFlowManager.execute``'s
+    ExecutionResult: a trainer returns its losses and no output series): one float64 file per loss, named after it.
+    The variables and their gradients are the step's state, not its result; they are not written."""
+    os.makedirs(path, exist_ok=True)
+    for name, value in res.losses.items():
+        np.save(os.path.join(path, "loss.{}.npy".format(re.sub(r"[^A-Za-z0-9_.-]+", "_", name))),
+                np.array([value], dtype=np.float64))
+
+
+def full_legs(args, dp, rank, world, dev, lib, model, tfm, pool, uploader, step, timed, fresh, barrier):
+    """What ``--full`` measures after the headline's timed steps (module docstring); returns the fields it adds to
+    rank 0's line (None on the other ranks, which take part in the collectives of the data-parallel legs)."""
+    from neuralmonkey_amd import _lib, ops, synthetic
     from neuralmonkey_amd.dataset import Dataset
-    from neuralmonkey_amd.input_pipeline import Prefetcher
-    dp = distributed.init_from_env()
-    rank = dp.rank if dp else 0
-    world = dp.world_size if dp else 1
-    if world != args.gpus:
-        raise SystemExit("--gpus {} but WORLD_SIZE={}".format(args.gpus, world))
-    # one rank per GPU; ranks beyond the visible devices wrap around (only meaningful with
-    # NM_DIST_BACKEND=gloo, the single-GPU smoke test of the multi-rank code path)
-    local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
-    torch.cuda.set_device(local)
-    dev = "cuda:{}".format(local)
-    lib = _lib.load()
-    if args.scaling == "strong":
-        if args.batch % world:
-            raise SystemExit("--scaling strong: --batch {} is not divisible by {} GPUs".format(args.batch, world))
-        args.batch //= world                  # from here on: sentences per GPU
-
     h = args.hidden
-    model = synthetic.build_translation_model(vocab_src=args.vocab, vocab_tgt=args.vocab, emb=h, rnn=h,
-                                              max_len=args.length, beam_size=5, max_steps=args.length,
-                                              length_normalization=0.6, l2_weight=1e-8, clip_norm=1.0,
-                                              device=dev, seed=1234)
-    store = model.tf_manager.sessions[0].store
-    synthetic.load_baseline_weights(store, seed=1234, std=0.05)          # BASELINE.md section 3
-    if dp:
-        dp.broadcast_parameters(store)
-    tfm, trainer = model.tf_manager, model.trainer
-    feedables = trainer.feedables
-    # NUM_BATCHES distinct batches of pre-indexed int32 ids per rank
-    pool = [synthetic.synthetic_dataset(seed=1234 + 1000 * i + rank, batch=args.batch, src_len=args.length,
-                                        tgt_len=args.length, vocab=args.vocab, ragged=False)
-            for i in range(NUM_BATCHES)]
-    tokens_local = args.batch * args.length               # every target has len-1 tokens + </s>
-    tokens_global = tokens_local * world
-
-    def fresh(d):
-        """The same data as a NEW batch object: no feed dict cached on it, nothing resident in HBM."""
-        return Dataset(d.name, {k: list(d.get_series(k)) for k in d.series}, d.batching)
-
-    def step(batch):
-        return tfm.execute(batch, feedables, [trainer], train=True)[0]
-
-    def barrier():
-        if dp:
-            torch.distributed.barrier()
-        torch.cuda.synchronize()
-
-    def timed(batches):
-        barrier()
-        t0 = time.perf_counter()
-        for b in batches:
-            out = step(b)
-        barrier()
-        return time.perf_counter() - t0, out
+    tokens_local = args.batch * args.length
+    store = tfm.sessions[0].store
 
     # ---- beam-5 decode throughput (emitted rank-1 tokens up to and incl. </s>)
     beam_tok_s = beam_ms_per_batch = beam_b1_ms = None
@@ -672,37 +646,11 @@ def main():
             beam_b1_ms = (time.perf_counter() - t1) / n1 * 1e3
         logit_b[2] = saved_end_bias
 
-    # ---- training: the headline number.  All NUM_BATCHES batches are uploaded first (feed dicts built,
-    # ids resident in HBM), then W warm-up steps (>= 2: eager pass with allocations + HIP-graph capture
-    # pass), then EXACTLY K timed steps rotating through the distinct batches.
-    uploader = Prefetcher(tfm, feedables, train=True)
-    for b in pool:
-        uploader.upload(b)
-    for i in range(max(args.warmup, 2)):
-        step(pool[i % NUM_BATCHES])
-    if dp:
-        dp.timing = True
-        dp.exchange_report()
-    elapsed, res = timed(pool[i % NUM_BATCHES] for i in range(args.steps))
-    dp_report = None
-    if dp:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-        dp_report = dp.exchange_report()
-        dp_report["how"] = ("allreduce_exposed_ms: HIP events on rank 0's compute stream around the point where the "
-                            "optimizer has to wait for the gradient collectives (mean over the timed steps) = the part "
-                            "of the exchange that the backward pass did not hide; bytes: flat gradient buffer per "
-                            "step and rank, early_bytes: the spans whose collective starts inside the backward pass; "
-                            "optimizer: 'sharded' = reduce-scatter -> clip + Adam on this rank's slices of the flat "
-                            "buffers -> all-gather of the parameters (NM_DP_SHARDED=0: all-reduce + the whole update on "
-                            "every rank); optimizer_ms: HIP events around norms + update (+ all-gather); "
-                            "exchanged_bytes_per_rank: what a rank sends per step with ring collectives")
-
     # ---- the other scaling mode in the same run (N > 1): BASELINE.json's wording is the STRONG split (one
     # minibatch of --batch sentences sharded over the GPUs); `value` above is the weak one unless --scaling strong
     other = None
     if dp and world > 1 and args.scaling == "weak" and args.batch % world == 0:
+        dp.timing = True
         sb = args.batch // world
         spool = [synthetic.synthetic_dataset(seed=4321 + 1000 * i + rank, batch=sb, src_len=args.length,
                                              tgt_len=args.length, vocab=args.vocab, ragged=False)
@@ -716,13 +664,12 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         t_strong = float(t.item())
         rep = dp.exchange_report()
+        dp.timing = False
         other = {"scaling": "strong", "sentences_per_gpu": sb, "global_batch": args.batch,
                  "ms_per_step": t_strong / args.steps * 1e3,
                  "value": sb * args.length * world * args.steps / t_strong, "unit": "tokens/s",
                  "allreduce_exposed_ms": rep["allreduce_exposed_ms"], "optimizer": rep.get("optimizer"),
                  "optimizer_ms": rep.get("optimizer_ms")}
-    if dp:
-        dp.timing = False
 
     # ---- the same step fed from the host inside the timed loop (rank 0 reports; not `value`)
     fresh_ms = strings_ms = None
@@ -902,21 +849,8 @@ def main():
                 rocprof_files.append(os.path.relpath(path, ROOT))
         dstep_bytes = decoder_step_bytes(args.batch, args.length, h, args.vocab)
         dstep_us = greedy_ms * 1e3 / args.length
-        line = {
-            "metric": "target tokens/sec/node (train), 512-hid GRU+attn",
-            "value": tokens_global * args.steps / elapsed, "unit": "tokens/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "translation.ini-shape: biGRU-{h} enc + Bahdanau attn + GRU-{h} dec, "
-                                   "B={b}/GPU, src_len=tgt_len={l}, V={v}, weights N(0,0.05)/orthogonal "
-                                   "(BASELINE.md 3), CrossEntropyTrainer(l2=1e-8, clip_norm=1.0) + Adam(1e-4), "
-                                   "one optimizer step per step, {n} distinct HBM-resident batches in "
-                                   "rotation".format(h=h, b=args.batch, l=args.length, v=args.vocab, n=NUM_BATCHES),
-                       "global_batch": args.batch * world, "seq_len": args.length,
-                       "parallelism": "dp{}".format(world)},
-            "loss": res.losses["decoder - cost"],
-            "dp": dp_report, "other_scaling": other,
+        fields = {
+            "other_scaling": other,
             "ms_per_step_fresh": fresh_ms, "ms_per_step_strings": strings_ms,
             "beam5_decode_tok_s": beam_tok_s, "beam5_ms_per_batch": beam_ms_per_batch,
             "beam5_batch1_ms_per_sentence": beam_b1_ms,
@@ -968,14 +902,6 @@ def main():
                          "warm_how": "inside a greedy decode of one B={} batch, {} steps, launched eagerly".format(
                              args.batch, args.length),
                          "algorithmic_bytes_per_launch": step_bytes},
-            "roofline_train": (lambda fl, sec: {
-                "what": "the timed region of `value`: one whole training step (forward, backward, clip, Adam) against "
-                        "the fp32 matrix-core peak; flops = 2 x multiply-adds of every dense product, forward + "
-                        "backward (synthetic.translation_train_flops: the Bahdanau energies / contexts on the vector "
-                        "units are not counted)",
-                "bound": "mfma", "flops_per_step": fl, "achieved": fl / sec / 1e12, "peak": MFMA_F32_PEAK_TF,
-                "unit": "TFLOP/s", "frac": fl / sec / 1e12 / MFMA_F32_PEAK_TF})(
-                    synthetic.translation_train_flops(args.batch, args.length, args.vocab, h), elapsed / args.steps),
             "roofline_step": {"what": "one greedy decoder step (GRU + attention + output projection + logits + "
                                       "argmax), HIP-graph replayed", "bound": "hbm",
                               "algorithmic_bytes_per_step": dstep_bytes, "us_per_step": dstep_us,
@@ -995,12 +921,133 @@ def main():
                     legs[name] = fn()
                 except Exception as exc:                  # pragma: no cover  (never hide the headline number)
                     legs[name] = {"error": repr(exc)}
-            line["configs"] = legs
+            fields["configs"] = legs
         if world == 1 and not args.no_cpu_baseline:
             try:
-                line["cpu_baseline"] = cpu_baseline(args)
+                fields["cpu_baseline"] = cpu_baseline(args)
             except Exception as exc:                      # pragma: no cover  (never hide the GPU number)
-                line["cpu_baseline"] = {"value": None, "error": repr(exc)}
+                fields["cpu_baseline"] = {"value": None, "error": repr(exc)}
+        return fields
+    return None
+
+
+def main():
+    args = parse()
+    from neuralmonkey_amd import _lib, distributed, synthetic
+    from neuralmonkey_amd.dataset import Dataset
+    from neuralmonkey_amd.input_pipeline import Prefetcher
+    dp = distributed.init_from_env()
+    rank = dp.rank if dp else 0
+    world = dp.world_size if dp else 1
+    if world != args.gpus:
+        raise SystemExit("--gpus {} but WORLD_SIZE={}".format(args.gpus, world))
+    # one rank per GPU; ranks beyond the visible devices wrap around (only meaningful with
+    # NM_DIST_BACKEND=gloo, the single-GPU smoke test of the multi-rank code path)
+    local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
+    torch.cuda.set_device(local)
+    dev = "cuda:{}".format(local)
+    lib = _lib.load()
+    if args.scaling == "strong":
+        if args.batch % world:
+            raise SystemExit("--scaling strong: --batch {} is not divisible by {} GPUs".format(args.batch, world))
+        args.batch //= world                  # from here on: sentences per GPU
+
+    h = args.hidden
+    model = synthetic.build_translation_model(vocab_src=args.vocab, vocab_tgt=args.vocab, emb=h, rnn=h,
+                                              max_len=args.length, beam_size=5, max_steps=args.length,
+                                              length_normalization=0.6, l2_weight=1e-8, clip_norm=1.0,
+                                              device=dev, seed=1234)
+    store = model.tf_manager.sessions[0].store
+    synthetic.load_baseline_weights(store, seed=1234, std=0.05)          # BASELINE.md section 3
+    if dp:
+        dp.broadcast_parameters(store)
+    tfm, trainer = model.tf_manager, model.trainer
+    feedables = trainer.feedables
+    # NUM_BATCHES distinct batches of pre-indexed int32 ids per rank
+    pool = [synthetic.synthetic_dataset(seed=1234 + 1000 * i + rank, batch=args.batch, src_len=args.length,
+                                        tgt_len=args.length, vocab=args.vocab, ragged=False)
+            for i in range(NUM_BATCHES)]
+    tokens_local = args.batch * args.length               # every target has len-1 tokens + </s>
+    tokens_global = tokens_local * world
+
+    def fresh(d):
+        """The same data as a NEW batch object: no feed dict cached on it, nothing resident in HBM."""
+        return Dataset(d.name, {k: list(d.get_series(k)) for k in d.series}, d.batching)
+
+    def step(batch):
+        return tfm.execute(batch, feedables, [trainer], train=True)[0]
+
+    def barrier():
+        if dp:
+            torch.distributed.barrier()
+        torch.cuda.synchronize()
+
+    def timed(batches):
+        barrier()
+        t0 = time.perf_counter()
+        for b in batches:
+            out = step(b)
+        barrier()
+        return time.perf_counter() - t0, out
+
+    # ---- training: the headline number.  All NUM_BATCHES batches are uploaded first (feed dicts built,
+    # ids resident in HBM), then W warm-up steps (>= 2: eager pass with allocations + HIP-graph capture
+    # pass), then EXACTLY K timed steps rotating through the distinct batches.
+    uploader = Prefetcher(tfm, feedables, train=True)
+    for b in pool:
+        uploader.upload(b)
+    for i in range(max(args.warmup, 2)):
+        step(pool[i % NUM_BATCHES])
+    if dp:
+        dp.timing = True
+        dp.exchange_report()
+    elapsed, res = timed(pool[i % NUM_BATCHES] for i in range(args.steps))
+    dp_report = None
+    if dp:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+        dp_report = dp.exchange_report()
+        dp_report["how"] = ("allreduce_exposed_ms: HIP events on rank 0's compute stream around the point where the "
+                            "optimizer has to wait for the gradient collectives (mean over the timed steps) = the part "
+                            "of the exchange that the backward pass did not hide; bytes: flat gradient buffer per "
+                            "step and rank, early_bytes: the spans whose collective starts inside the backward pass; "
+                            "optimizer: 'sharded' = reduce-scatter -> clip + Adam on this rank's slices of the flat "
+                            "buffers -> all-gather of the parameters (NM_DP_SHARDED=0: all-reduce + the whole update on "
+                            "every rank); optimizer_ms: HIP events around norms + update (+ all-gather); "
+                            "exchanged_bytes_per_rank: what a rank sends per step with ring collectives")
+        dp.timing = False
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    extra = full_legs(args, dp, rank, world, dev, lib, model, tfm, pool, uploader, step, timed, fresh,
+                      barrier) if args.full else None
+
+    if rank == 0:
+        line = {
+            "metric": "target tokens/sec/node (train), 512-hid GRU+attn",
+            "value": tokens_global * args.steps / elapsed, "unit": "tokens/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "translation.ini-shape: biGRU-{h} enc + Bahdanau attn + GRU-{h} dec, "
+                                   "B={b}/GPU, src_len=tgt_len={l}, V={v}, weights N(0,0.05)/orthogonal "
+                                   "(BASELINE.md 3), CrossEntropyTrainer(l2=1e-8, clip_norm=1.0) + Adam(1e-4), "
+                                   "one optimizer step per step, {n} distinct HBM-resident batches in "
+                                   "rotation".format(h=h, b=args.batch, l=args.length, v=args.vocab, n=NUM_BATCHES),
+                       "global_batch": args.batch * world, "seq_len": args.length,
+                       "parallelism": "dp{}".format(world)},
+            "loss": res.losses["decoder - cost"],
+            "dp": dp_report,
+            "roofline_train": (lambda fl, sec: {
+                "what": "the timed region of `value`: one whole training step (forward, backward, clip, Adam) against "
+                        "the fp32 matrix-core peak; flops = 2 x multiply-adds of every dense product, forward + "
+                        "backward (synthetic.translation_train_flops: the Bahdanau energies / contexts on the vector "
+                        "units are not counted)",
+                "bound": "mfma", "flops_per_step": fl, "achieved": fl / sec / 1e12, "peak": MFMA_F32_PEAK_TF,
+                "unit": "TFLOP/s", "frac": fl / sec / 1e12 / MFMA_F32_PEAK_TF})(
+                    synthetic.translation_train_flops(args.batch, args.length, args.vocab, h), elapsed / args.steps),
+        }
+        line.update(extra or {})
         print(json.dumps(line), flush=True)
     if dp:
         distributed.shutdown()
