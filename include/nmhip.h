@@ -708,6 +708,40 @@ int nm_allreduce_bucket(nm_comm* comm, void* stream, float* buf, int64_t count);
 int nm_allreduce_wait(nm_comm* comm, void* stream);
 int nm_allreduce_destroy(nm_comm* comm);
 
+/* ---- sentence CNN encoder (csrc/nm_conv.hip) ------------------------------------------------------------------
+ * encoders/sentence_cnn_encoder.py:113-143 (per filter width tf.nn.conv1d stride 1 SAME + bias_add + relu, then
+ * tf.nn.max_pool over segments of `segment` positions, stride `segment`, SAME; tf.concat of the widths) and
+ * :188-196 + :164-167 (SAME max-pool of the token mask, ceil(lengths / segment)).
+ * x [B, S, E] rows of ldx floats; filter i: W[i] [widths[i], E, counts[i]] (TF's conv1d filter layout), bias[i]
+ * [counts[i]]; pooled / argmax [B, S', ldp], S' = ceil(S / segment), ldp = sum of counts, width i in columns
+ * [counts[0] + .. + counts[i-1], +counts[i]); argmax holds the position t of each pooled maximum (ties: lowest t).
+ * SAME padding: the convolution pads (w - 1) / 2 positions before; the pooling pads (S' segment - S) / 2 before.
+ * mask [B, S] / lengths [B] -> mask_out [B, S'] / seq_lens [B], each optional.  W, bias: HOST arrays of device
+ * pointers.  algo 0 auto / 1 MFMA kernels (widths <= 8, segment <= 128) / 2 scalar kernels (any size). */
+int nm_conv1d_pool_fwd(void* stream, const float* x, int64_t ldx, int B, int S, int E, int segment, int nw,
+                       const int* widths, const int* counts, const float* const* W, const float* const* bias,
+                       float* pooled, int* argmax, int64_t ldp, const float* mask, const int* lengths, float* mask_out,
+                       int* seq_lens, int algo);
+/* bytes of the weight-gradient workspace of nm_conv1d_pool_bwd (fixed-order slabs of the position split) */
+int64_t nm_conv1d_wgrad_workspace_bytes(int B, int S, int E, int nw, const int* widths, const int* counts);
+/* tf.gradients of the above: dz [B, S, ldp] (out) = dpooled routed to the argmax, gated by pooled > 0 (ReluGrad of
+ * the relu output); dx (+)= the transposed convolution of every width (optional); dW[i] / dbias[i] (+)= the filter
+ * and bias gradients (optional, HOST arrays of device pointers; deterministic: no float atomics). */
+int nm_conv1d_pool_bwd(void* stream, const float* x, int64_t ldx, int B, int S, int E, int segment, int nw,
+                       const int* widths, const int* counts, const float* const* W, const float* pooled,
+                       const int* argmax, const float* dpooled, int64_t ldp, float* dz, float* dx, int accumulate_dx,
+                       float* const* dW, float* const* dbias, int accumulate_params, void* workspace,
+                       int64_t workspace_bytes, int algo);
+/* nn/highway.py:44-57, the point-wise part of a highway layer after its two products zt = x.W_T, zh = x.W_H:
+ * T = sigmoid(zt + bt), H = relu(zh + bh), y = H T + x (1 - T); tsave / hsave [rows, cols] (contiguous) keep T, H.
+ * y has x's row stride. */
+int nm_highway_fwd(void* stream, const float* zt, const float* zh, int64_t ldz, const float* x, int64_t ldx,
+                   const float* bt, const float* bh, float* y, float* tsave, float* hsave, int64_t rows, int64_t cols);
+/* its gradient: dzt = dy (H - x) T (1 - T), dzh = dy T [H > 0], dx (+)= dy (1 - T) (the carry term); dy has x's
+ * row stride, dzt / dzh rows of ldz floats. */
+int nm_highway_bwd(void* stream, const float* dy, const float* x, int64_t ldx, const float* tsave, const float* hsave,
+                   float* dzt, float* dzh, int64_t ldz, float* dx, int64_t rows, int64_t cols, int accumulate_dx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,11 @@ SIGNATURES = {
     "nm_dec_step_cluster_workspace_bytes": (L, [L, L]),
     "nm_prof_stream_read": (I, [P, P, L, P]),
     "nm_beam_topk_step_tiles": (I, [P, P, L, P, L, L, L, L, P, P, P, P, I, P, P, P, P, P, P, P, P, L, P, P, P]),
+    "nm_conv1d_pool_fwd": (I, [P, P, L, I, I, I, I, I, P, P, P, P, P, P, L, P, P, P, P, I]),
+    "nm_conv1d_wgrad_workspace_bytes": (L, [I, I, I, I, P, P]),
+    "nm_conv1d_pool_bwd": (I, [P, P, L, I, I, I, I, I, P, P, P, P, P, P, L, P, P, I, P, P, I, P, L, I]),
+    "nm_highway_fwd": (I, [P, P, P, L, P, L, P, P, P, P, P, L, L]),
+    "nm_highway_bwd": (I, [P, P, P, L, P, P, P, P, L, P, L, L, I]),
 }
 
 

@@ -975,3 +975,76 @@ def xent(tape: Tape, logits: Var, targets: torch.Tensor, weights: Optional[torch
     if tape.recording:
         logits.grad = logits.data
     return loss_rows
+
+
+def conv1d_relu_maxpool(tape: Tape, x: Var, filters: Sequence[Var], biases: Sequence[Var], bsz: int, slen: int,
+                        segment: int, mask: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None):
+    """encoders/sentence_cnn_encoder.py:113-143: for every filter W_i [w_i, E, n_i] tf.nn.conv1d (stride 1, SAME) +
+    bias + relu, SAME max-pool over segments, concatenated: x [B*S, E] -> pooled Var [B*S', sum n_i], all widths in
+    ONE launch (nm_conv1d_pool_fwd).  With ``mask`` / ``lengths``: also the pooled mask [B, S'] and ceil(lengths /
+    segment) [B] from the same call.  Returns (pooled, pooled mask or None, pooled lengths or None)."""
+    e = x.shape[1]
+    sp, _ = ops.conv1d_pool_shape(slen, segment)
+    width = sum(int(w.shape[2]) for w in filters)
+    out = tape.new((bsz * sp, width))
+    arg = tape.buf((bsz * sp, width), torch.int32)
+    mask_out = tape.buf((bsz, sp)) if mask is not None else None
+    lens_out = tape.buf((bsz,), torch.int32) if lengths is not None else None
+    x3 = x.data.view(bsz, slen, e)
+    ops.conv1d_pool_fwd(x3, [w.data for w in filters], [b.data for b in biases], segment, out.data, arg, mask=mask,
+                        lengths=lengths, mask_out=mask_out, seq_lens=lens_out)
+
+    def bwd():
+        if out.grad is None:
+            return
+        params = any(w.needs_grad for w in filters)
+        dz = tape.buf((bsz, slen, width))
+        gx, acc = tape.grad_slot(x) if x.needs_grad else (None, False)
+        ws = None
+        if params:
+            ws = tape.buf((max(1, ops.conv1d_wgrad_workspace_floats(bsz, slen, e, [w.data for w in filters])),))
+        ops.conv1d_pool_bwd(x3, [w.data for w in filters], segment, out.data, arg, out.grad, dz,
+                            dx=None if gx is None else gx.view(bsz, slen, e), accumulate_dx=acc,
+                            dweights=[tape.grad(w) for w in filters] if params else None,
+                            dbiases=[tape.grad(b) for b in biases] if params else None, accumulate_params=True,
+                            workspace=ws)
+    tape.record(bwd)
+    return out, mask_out, lens_out
+
+
+def highway(tape: Tape, x: Var, w_t: Var, b_t: Var, w_h: Var, b_h: Var) -> Var:
+    """nn/highway.py:6-57: T = sigmoid(x.W_T + b_T), H = relu(x.W_H + b_H), y = H T + x (1 - T).  The two products in
+    one launch (nm_gemm_f32_group) where the operands allow it, the point-wise part in one kernel that keeps T and H
+    (nm_highway_fwd); backward: one point-wise kernel for dz_T, dz_H and the carry term of dx (nm_highway_bwd), the
+    products' transposes through ``linear``'s paths (weight gradients deferred to the grouped launch)."""
+    rows, d = x.shape
+    z = tape.buf((2, rows, d))
+    xd = x.data
+    grouped = (xd.stride(1) == 1 and xd.stride(0) % 4 == 0 and d % 4 == 0 and xd.data_ptr() % 16 == 0
+               and w_t.data.data_ptr() % 16 == 0 and w_h.data.data_ptr() % 16 == 0 and z.data_ptr() % 16 == 0)
+    if grouped:
+        ops.gemm_group([(xd, w_t.data, z[0]), (xd, w_h.data, z[1])], accumulate=False)
+    else:
+        ops.gemm(xd, w_t.data, out=z[0])
+        ops.gemm(xd, w_h.data, out=z[1])
+    out = tape.new((rows, d))
+    t_save, h_save = tape.buf((rows, d)), tape.buf((rows, d))
+    ops.highway_fwd(z[0], z[1], xd, b_t.data, b_h.data, out.data, t_save, h_save)
+
+    def bwd():
+        if out.grad is None:
+            return
+        dz = tape.buf((2, rows, d))
+        gx, acc = tape.grad_slot(x) if x.needs_grad else (None, False)
+        carry = gx if gx is not None else tape.buf((rows, d))
+        ops.highway_bwd(out.grad, xd, t_save, h_save, dz[0], dz[1], carry, accumulate_dx=acc)
+        if gx is not None:
+            ops.gemm(dz[0], w_t.data, out=gx, trans_b=True, accumulate=True)
+            ops.gemm(dz[1], w_h.data, out=gx, trans_b=True, accumulate=True)
+        for w, b, g in ((w_t, b_t, dz[0]), (w_h, b_h, dz[1])):
+            if w.needs_grad:
+                tape.defer_wgrad(xd, g, tape.grad(w), True)
+            if b.needs_grad:
+                tape.defer_bias(g, tape.grad(b))
+    tape.record(bwd)
+    return out

@@ -629,6 +629,8 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
         tape.record(bwd)
         return out, final
 
+    # (encoders/sentence_cnn_encoder.py reuses _general_layer and the three *_cluster_layer methods above for its GRU
+    # layer: they may read nothing of ``self`` beyond rnn_specs, _cells, var_name and the cluster-layer methods)
     def _general_layer(self, tape, x, bsz: int, slen: int, lengths, layer: int, train: bool):
         """rnn_layer (recurrent.py:71-110) on the tape.  x: Var [B*S, D] -> (outputs Var
         [B*S, ndir*H], final Var [B, ndir*H])."""

@@ -1465,3 +1465,92 @@ class OptimizerTables:
     def chunk_range(self, lo, hi):
         """The chunks whose elements lie in [lo, hi) of the flat buffer: (begin, end)."""
         return chunk_range_of(self._starts_host, self._lens_host, lo, hi)
+
+
+# ---- sentence CNN encoder (csrc/nm_conv.hip) ------------------------------------------------------------------------
+def _conv_tables(weights):
+    """(widths, counts, pointer table) of filters W_i [w_i, E, n_i] as host arrays for the conv entry points."""
+    n = len(weights)
+    for w in weights:
+        _f32(w)
+        assert w.dim() == 3 and w.is_contiguous(), "conv filters are contiguous [w, E, n]"
+    widths = (ctypes.c_int * n)(*[int(w.shape[0]) for w in weights])
+    counts = (ctypes.c_int * n)(*[int(w.shape[2]) for w in weights])
+    return widths, counts, (ctypes.c_void_p * n)(*[w.data_ptr() for w in weights])
+
+
+def _ptrs(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def conv1d_pool_shape(slen: int, segment: int):
+    """(S', pad before) of the SAME max-pool over ``segment`` positions with stride ``segment``."""
+    sp = (slen + segment - 1) // segment
+    return sp, (sp * segment - slen) // 2
+
+
+def conv1d_pool_fwd(x, weights, biases, segment, pooled, argmax, mask=None, lengths=None, mask_out=None,
+                    seq_lens=None, algo=0):
+    """pooled [B, S', sum n_i] (+ int32 argmax) = per width max-pool(relu(conv1d_SAME(x [B, S, E], W_i) + b_i)), all
+    widths in one launch (nm_conv1d_pool_fwd); optionally the pooled mask [B, S'] and ceil(lengths / segment)."""
+    lib = _lib.load()
+    _f32(x), _f32(pooled), _i32(argmax)
+    bsz, slen, e = x.shape
+    assert x.stride(2) == 1 and x.stride(0) == slen * x.stride(1), "x: [B, S, E] rows of one stride"
+    assert pooled.is_contiguous() and argmax.is_contiguous() and pooled.shape == argmax.shape
+    widths, counts, wtab = _conv_tables(weights)
+    assert all(_f32(b).is_contiguous() and b.numel() == w.shape[2] for b, w in zip(biases, weights))
+    if mask is not None:
+        assert mask.is_contiguous() and mask_out is not None and mask_out.is_contiguous()
+    _lib.check(lib.nm_conv1d_pool_fwd(_stream(), x.data_ptr(), x.stride(1), bsz, slen, e, int(segment), len(weights),
+                                      widths, counts, wtab, _ptrs(biases), pooled.data_ptr(), argmax.data_ptr(),
+                                      pooled.shape[-1], _p(mask), _p(lengths), _p(mask_out), _p(seq_lens), int(algo)),
+               "nm_conv1d_pool_fwd")
+    return pooled, argmax
+
+
+def conv1d_wgrad_workspace_floats(bsz, slen, e, weights) -> int:
+    widths, counts, _ = _conv_tables(weights)
+    return int(_lib.load().nm_conv1d_wgrad_workspace_bytes(bsz, slen, e, len(weights), widths, counts)) // 4
+
+
+def conv1d_pool_bwd(x, weights, segment, pooled, argmax, dpooled, dz, dx=None, accumulate_dx=False, dweights=None,
+                    dbiases=None, accumulate_params=True, workspace=None, algo=0):
+    """The gradient of ``conv1d_pool_fwd``: dz [B, S, sum n_i] (scratch, written whole) = dpooled at the argmax where
+    pooled > 0; dx (+)= the transposed convolution of every width; dW_i / db_i (+)= the filter / bias gradients
+    (nm_conv1d_pool_bwd; deterministic).  ``workspace``: conv1d_wgrad_workspace_floats floats."""
+    lib = _lib.load()
+    bsz, slen, e = x.shape
+    assert x.stride(2) == 1 and x.stride(0) == slen * x.stride(1)
+    assert dpooled.is_contiguous() and dz.is_contiguous() and dz.shape[-1] == pooled.shape[-1]
+    assert dx is None or (dx.stride(1) == x.stride(1) and dx.stride(0) == x.stride(0) and dx.stride(2) == 1)
+    widths, counts, wtab = _conv_tables(weights)
+    dw_tab = db_tab = None
+    if dweights is not None:
+        assert all(g.is_contiguous() and g.shape == w.shape for g, w in zip(dweights, weights))
+        dw_tab, db_tab = _ptrs(dweights), _ptrs(dbiases)
+    _lib.check(lib.nm_conv1d_pool_bwd(_stream(), x.data_ptr(), x.stride(1), bsz, slen, e, int(segment), len(weights),
+                                      widths, counts, wtab, pooled.data_ptr(), argmax.data_ptr(), dpooled.data_ptr(),
+                                      pooled.shape[-1], dz.data_ptr(), _p(dx), int(accumulate_dx), dw_tab, db_tab,
+                                      int(accumulate_params), _p(workspace),
+                                      0 if workspace is None else workspace.numel() * 4, int(algo)),
+               "nm_conv1d_pool_bwd")
+
+
+def highway_fwd(zt, zh, x, bt, bh, y, tsave, hsave):
+    """y = relu(zh + bh) T + x (1 - T), T = sigmoid(zt + bt) (nm_highway_fwd); T, H kept for the backward pass."""
+    rows, cols, ldx = _rc(x)
+    assert _rc(y)[2] == ldx and _rc(zh)[2] == _rc(zt)[2] and tsave.is_contiguous() and hsave.is_contiguous()
+    _lib.check(_lib.load().nm_highway_fwd(_stream(), zt.data_ptr(), zh.data_ptr(), _rc(zt)[2], x.data_ptr(), ldx,
+                                          bt.data_ptr(), bh.data_ptr(), y.data_ptr(), tsave.data_ptr(),
+                                          hsave.data_ptr(), rows, cols), "nm_highway_fwd")
+    return y
+
+
+def highway_bwd(dy, x, tsave, hsave, dzt, dzh, dx, accumulate_dx=False):
+    """dzt, dzh (the gradients of the two products' outputs) and the carry term of dx (nm_highway_bwd)."""
+    rows, cols, ldx = _rc(x)
+    assert _rc(dy)[2] == ldx and _rc(dx)[2] == ldx and _rc(dzh)[2] == _rc(dzt)[2]
+    _lib.check(_lib.load().nm_highway_bwd(_stream(), dy.data_ptr(), x.data_ptr(), ldx, tsave.data_ptr(),
+                                          hsave.data_ptr(), dzt.data_ptr(), dzh.data_ptr(), _rc(dzt)[2], dx.data_ptr(),
+                                          rows, cols, int(accumulate_dx)), "nm_highway_bwd")
