@@ -87,6 +87,10 @@ std::pair<hipEvent_t, hipEvent_t>* nm_prof_next_pair(NmCtx* c);
 static inline bool nm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static inline int nm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// Kernels that put rows on gridDim.y: the dimension holds at most 65535 blocks, so a launch takes that many rows of
+// blocks and every block walks the rows r, r + gridDim.y, ... (a caller's row count is not bounded).
+#define NM_MAX_GRID_Y 65535
+static inline unsigned nm_grid_rows(int64_t rows) { return (unsigned)(rows < NM_MAX_GRID_Y ? rows : NM_MAX_GRID_Y); }
 
 // ---- device helpers -------------------------------------------------------
 __device__ __forceinline__ bool nm_aligned16_dev(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

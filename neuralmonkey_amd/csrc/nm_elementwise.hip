@@ -411,16 +411,16 @@ extern "C" int nm_layer_norm_fwd(void* stream, const float* x, int64_t ldx, cons
 // ---------------------------------------------------------------------------
 __global__ void copy_cols_kernel(const float* __restrict__ src, long lds_, float* __restrict__ dst,
                                  long ldd, long rows, int w) {
-    const long r = blockIdx.y;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < w) dst[r * ldd + c] = src[r * lds_ + c];
+    if (c >= w) return;
+    for (long r = blockIdx.y; r < rows; r += gridDim.y) dst[r * ldd + c] = src[r * lds_ + c];
 }
 
 extern "C" int nm_copy_cols(void* stream, const float* src, int64_t ld_src, float* dst, int64_t ld_dst,
                             int64_t rows, int64_t width) {
     NM_REQUIRE(src && dst && rows >= 0 && width >= 0, "nm_copy_cols: bad args");
     if (rows == 0 || width == 0) return NM_OK;
-    hipLaunchKernelGGL(copy_cols_kernel, dim3(nm_cdiv(width, 256), (unsigned)rows), dim3(256), 0,
+    hipLaunchKernelGGL(copy_cols_kernel, dim3(nm_cdiv(width, 256), nm_grid_rows(rows)), dim3(256), 0,
                        nm_stream(stream), src, (long)ld_src, dst, (long)ld_dst, (long)rows, (int)width);
     NM_LAUNCH_CHECK("nm_copy_cols");
 }
@@ -444,6 +444,12 @@ __global__ __launch_bounds__(1024) void reduce_sum_kernel(const float* __restric
 }
 
 // two-stage variant for long vectors: 64 fixed slices -> library-owned partials -> final sum
+// ONE array for every stream of the process: two long reductions in flight at the same time would mix their partials.
+// They cannot overlap today: every ops.reduce_sum call (the loss sums of the decoders, the attention-bias gradient in
+// attention/feed_forward.py, directly and in its tape closures) is made on the session's main stream -- none sits
+// inside a runtime.Session.side() block or in work handed to defer_side, and the look-ahead stream evaluates the
+// encoder side of a batch without a loss.  A caller that puts nm_reduce_sum on a second stream has to give the call
+// its own partials first.
 __device__ float g_reduce_partials[64];
 __global__ __launch_bounds__(1024) void reduce_sum_slices_kernel(const float* __restrict__ x, long n) {
     __shared__ float sh[16];
@@ -483,17 +489,17 @@ extern "C" int nm_reduce_sum(void* stream, const float* x, int64_t n, float* out
 // ---------------------------------------------------------------------------
 __global__ void log_softmax_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ rmax,
                                    const float* __restrict__ rlse, float* __restrict__ out, long ldo,
-                                   int V) {
-    const long r = blockIdx.y;
+                                   long rows, int V) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < V) out[r * ldo + c] = (x[r * ldx + c] - rmax[r]) - rlse[r];
+    if (c >= V) return;
+    for (long r = blockIdx.y; r < rows; r += gridDim.y) out[r * ldo + c] = (x[r * ldx + c] - rmax[r]) - rlse[r];
 }
 
 extern "C" int nm_log_softmax(void* stream, const float* x, int64_t ldx, const float* rmax,
                               const float* rlse, float* out, int64_t ldo, int64_t rows, int64_t V) {
     NM_REQUIRE(x && rmax && rlse && out && rows >= 0 && V > 0, "nm_log_softmax: bad args");
     if (rows == 0) return NM_OK;
-    hipLaunchKernelGGL(log_softmax_kernel, dim3(nm_cdiv(V, 256), (unsigned)rows), dim3(256), 0,
-                       nm_stream(stream), x, (long)ldx, rmax, rlse, out, (long)ldo, (int)V);
+    hipLaunchKernelGGL(log_softmax_kernel, dim3(nm_cdiv(V, 256), nm_grid_rows(rows)), dim3(256), 0,
+                       nm_stream(stream), x, (long)ldx, rmax, rlse, out, (long)ldo, (long)rows, (int)V);
     NM_LAUNCH_CHECK("nm_log_softmax");
 }

@@ -129,6 +129,69 @@ def test_nematus_loops_against_the_oracle(dev, rows, steps, h, ndir, state_bias)
     assert np.abs(dh.cpu().numpy() - h0_64.grad.numpy()).max() <= 1e-4 * max(gscale, np.abs(h0_64.grad.numpy()).max())
 
 
+@pytest.mark.parametrize("rows,steps,h,ndir", [(37, 7, 256, 2), (16, 6, 512, 1), (20, 9, 384, 2), (128, 12, 512, 2)])
+def test_lstm_loops_against_float64(dev, rows, steps, h, ndir):
+    """nm_lstm_seq_fwd / nm_lstm_seq_bwd called directly (ragged lengths, the second direction walks backwards) against
+    the float64 recurrence of oracle/pointwise_ref.py::lstm_cell and its autograd; tolerances as the NematusGRU loops."""
+    from neuralmonkey_amd import ops
+    from oracle import pointwise_ref as P
+    assert ops.gru_seq_supported(rows, h, ndir)
+    rng = np.random.default_rng(rows + 3 * steps + h)
+    xp = (rng.standard_normal((rows * steps, ndir * 4 * h)) * 0.8).astype(np.float32)
+    wh = (rng.standard_normal((ndir, h, 4 * h)) * (1.0 / h ** 0.5)).astype(np.float32)
+    lens = rng.integers(1, steps + 1, size=rows).astype(np.int32)
+    lens[0] = steps
+    d_out = rng.standard_normal((rows, steps, ndir * h)) * (np.arange(steps)[None, :] < lens[:, None])[:, :, None]
+    d_fin = rng.standard_normal((ndir, rows, h))
+    xp64 = torch.tensor(xp, dtype=torch.float64, requires_grad=True)
+    h0_64 = torch.zeros(ndir, rows, h, dtype=torch.float64, requires_grad=True)
+    lt, ar = torch.tensor(lens), torch.arange(rows)
+    want_out = torch.zeros(rows, steps, ndir * h, dtype=torch.float64)
+    want_fin, loss = [], 0.0
+    for d in range(ndir):
+        w64 = torch.tensor(wh[d], dtype=torch.float64)
+        xd = xp64.view(rows, steps, ndir, 4 * h)[:, :, d]
+        hh, cc = h0_64[d], torch.zeros(rows, h, dtype=torch.float64)
+        for t in range(steps):
+            pos = (lt - 1 - t).clamp(min=0) if d == 1 else torch.full((rows,), t)
+            live = (t < lt)[:, None]
+            c_new, h_new, _ = P.lstm_cell(xd[ar, pos] + hh @ w64, cc, 1.0)
+            hh, cc = torch.where(live, h_new, hh), torch.where(live, c_new, cc)
+            emitted = torch.where(live, h_new, torch.zeros_like(h_new))
+            loss = loss + (emitted * torch.tensor(d_out[ar, pos.numpy(), d * h:(d + 1) * h]) * live).sum()
+            idx = live[:, 0]
+            want_out[ar[idx], pos[idx], d * h:(d + 1) * h] = emitted.detach()[idx]
+        want_fin.append(hh.detach())
+        loss = loss + (hh * torch.tensor(d_fin[d])).sum()
+    loss.backward()
+    T = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+    xpd, whd, lengths = T(xp), T(wh), T(lens, torch.int32)
+    hcur = torch.zeros(ndir, rows, h, device=dev)
+    out = torch.zeros(rows, steps, ndir * h, device=dev)
+    gates = torch.empty(steps, ndir, rows, 4 * h, device=dev)
+    c_all = torch.empty(steps, ndir, rows, h, device=dev)
+    ws = torch.empty(ops.lstm_seq_workspace_floats(rows, h, ndir), device=dev)
+    x_strides = (4 * h, steps * ndir * 4 * h, ndir * 4 * h)
+    seq = (h, steps * ndir * h, ndir * h)
+    ops.lstm_seq_fwd(steps, ndir, rows, h, xpd, x_strides, torch.zeros_like(hcur), hcur, 0, gates[0], ndir * rows * 4 * h,
+                     c_all[0], ndir * rows * h, whd, ws, forget_bias=1.0, lengths=lengths, out=out, out_strides=seq)
+    torch.cuda.synchronize()
+    assert not ops.gru_seq_failed(ws)
+    scale = max(1.0, float(want_out.abs().max()))
+    assert np.abs(out.cpu().numpy() - want_out.numpy()).max() <= 2e-5 * scale
+    assert np.abs(hcur.cpu().numpy() - torch.stack(want_fin).numpy()).max() <= 2e-5 * scale
+    dh = T(d_fin)
+    dxp = torch.zeros(rows * steps, ndir * 4 * h, device=dev)
+    ops.lstm_seq_bwd(steps, ndir, rows, h, dh, T(d_out), seq, gates[0], ndir * rows * 4 * h, c_all[0], ndir * rows * h,
+                     dxp, x_strides, whd, ws, lengths=lengths)
+    torch.cuda.synchronize()
+    assert not ops.gru_seq_failed(ws)
+    want_dxp = xp64.grad.numpy()
+    gscale = np.abs(want_dxp).max()
+    assert np.abs(dxp.cpu().numpy() - want_dxp).max() <= 1e-4 * gscale
+    assert np.abs(dh.cpu().numpy() - h0_64.grad.numpy()).max() <= 1e-4 * max(gscale, np.abs(h0_64.grad.numpy()).max())
+
+
 @pytest.mark.parametrize("direction,h", [("bidirectional", 256), ("backward", 256), ("forward", 384),
                                          ("bidirectional", 300), ("forward", 260)])      # 300 / 260: padded to 384
 def test_encoder_layer_takes_the_loops_and_matches_the_model_oracle(dev, direction, h, monkeypatch):

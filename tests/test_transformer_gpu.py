@@ -22,6 +22,28 @@ VOCAB = 40
 
 
 # ------------------------------------------------------------------------------------------- kernels
+def _sdp_ref(q, k, v, mt, heads, dh, causal, keep, rpk, salt):
+    """Multi-head scaled dot-product attention of q [B,Tq,D] over k / v [B/rpk,Tk,D] (torch-CPU, differentiable)."""
+    b, tq, d = q.shape
+    bk, tk, _ = k.shape
+    split = lambda x, n: x.view(x.shape[0], x.shape[1], heads, dh).permute(0, 2, 1, 3)
+    qq = split(q / math.sqrt(dh), b)
+    kk = split(k, bk).repeat_interleave(rpk, 0)
+    vv = split(v, bk).repeat_interleave(rpk, 0)
+    e = qq @ kk.transpose(-1, -2)
+    if causal:
+        i = torch.arange(tq)[:, None]
+        j = torch.arange(tk)[None, :]
+        e = torch.where(j <= i + tk - tq, e, torch.full_like(e, -1e9))
+    m4 = mt.repeat_interleave(rpk, 0)[:, None, None, :]
+    e = e * m4 + (1 - m4) * -1e9
+    w = torch.softmax(e, -1)
+    wd = w
+    if keep < 1.0:
+        wd = w * torch.from_numpy(G.dropout_mask(w.numel(), keep, salt)).view(w.shape)
+    return (wd @ vv).permute(0, 2, 1, 3).reshape(b, tq, d), w
+
+
 @pytest.mark.parametrize("b,tq,tk,heads,dh,causal,masked,keep,rpk", [
     (3, 7, 7, 3, 2, True, True, 1.0, 1),          # transformer.ini: d=6, 3 heads
     (4, 9, 13, 2, 8, False, True, 1.0, 1),        # cross attention, Tq != Tk
@@ -61,24 +83,7 @@ def test_sdp_attention_fwd_bwd(dev, b, tq, tk, heads, dh, causal, masked, keep, 
     mt = torch.tensor(mask)
     salt = 4242
 
-    def ref():
-        split = lambda x, n: x.view(x.shape[0], x.shape[1], heads, dh).permute(0, 2, 1, 3)
-        qq = split(q / math.sqrt(dh), b)
-        kk = split(k, bk).repeat_interleave(rpk, 0)
-        vv = split(v, bk).repeat_interleave(rpk, 0)
-        e = qq @ kk.transpose(-1, -2)
-        if causal:
-            i = torch.arange(tq)[:, None]
-            j = torch.arange(tk)[None, :]
-            e = torch.where(j <= i + tk - tq, e, torch.full_like(e, -1e9))
-        m4 = mt.repeat_interleave(rpk, 0)[:, None, None, :]
-        e = e * m4 + (1 - m4) * -1e9
-        w = torch.softmax(e, -1)
-        wd = w
-        if keep < 1.0:
-            wd = w * torch.from_numpy(G.dropout_mask(w.numel(), keep, salt)).view(w.shape)
-        return (wd @ vv).permute(0, 2, 1, 3).reshape(b, tq, d), w
-    want_ctx, want_w = ref()
+    want_ctx, want_w = _sdp_ref(q, k, v, mt, heads, dh, causal, keep, rpk, salt)
     qd, kd, vd = (x.detach().to(dev) for x in (q, k, v))
     ctx = torch.empty((b, tq, d), device=dev)
     w = torch.empty((b, heads, tq, tk), device=dev)
@@ -95,6 +100,77 @@ def test_sdp_attention_fwd_bwd(dev, b, tq, tk, heads, dh, causal, masked, keep, 
     ops.sdp_attn_bwd(qd, kd, vd, mt.to(dev), w, g.to(dev), heads, dq, dk, dv, de, causal, keep, salt, accumulate=True)
     for got, want in ((dq, q.grad), (dk, k.grad), (dv, v.grad)):
         assert float((got.cpu() - want).abs().max()) < 2e-5 * max(float(want.abs().max()), 1.0)
+
+
+@pytest.mark.parametrize("b,tq,tk,heads,dh,causal,masked,keep,rpk", [
+    (3, 7, 7, 3, 2, True, True, 1.0, 1),          # the scalar kernels
+    (5, 12, 12, 8, 64, True, True, 0.8, 1),       # ... with attention dropout
+    (2, 70, 130, 1, 32, False, False, 1.0, 1),    # no mask
+    (3, 50, 50, 8, 64, True, True, 0.9, 1),       # matrix-core kernels
+    (2, 33, 17, 8, 64, True, True, 1.0, 1),       # odd key count
+    (6, 9, 40, 4, 64, False, True, 1.0, 3),       # several query rows per key batch (forward only)
+    (10, 1, 50, 8, 64, False, True, 1.0, 5),      # one query per row: a beam step against a cache
+    (7, 1, 37, 8, 64, True, True, 1.0, 1),
+])
+def test_sdp_attention_inside_caches_and_gradient_accumulation(dev, b, tq, tk, heads, dh, causal, masked, keep, rpk):
+    """The wrappers take batch strides larger than T * D: q / k / v / ctx are the first positions of longer caches
+    (what follows them is NaN: nothing past Tq / Tk may be read or written) and the mask row is wider than Tk.
+    nm_sdp_attn_bwd with accumulate=False writes into NaN-filled gradient caches (everything inside is overwritten,
+    nothing outside is touched) and with accumulate=True adds onto a non-zero base."""
+    from neuralmonkey_amd import ops
+    rng = np.random.default_rng(b * 100 + tq + 7)
+    d = heads * dh
+    bk = b // rpk
+    nrm = lambda *shape: torch.tensor(rng.standard_normal(shape).astype(np.float32))
+    q, k, v = nrm(b, tq, d), nrm(bk, tk, d), nrm(bk, tk, d)
+    q64, k64, v64 = (x.double().requires_grad_(True) for x in (q, k, v))        # the reference runs in float64
+    mask = np.ones((bk, tk), np.float32)
+    if masked:
+        for i in range(bk):
+            mask[i, rng.integers(1, tk + 1):] = 0
+    mt = torch.tensor(mask)
+    salt = 977
+    want_ctx, want_w = _sdp_ref(q64, k64, v64, mt.double(), heads, dh, causal, keep, rpk, salt)
+
+    def cache(x, extra):
+        """x [B,T,D] as the first T positions of a [B,T+extra,D] device buffer whose tail is NaN."""
+        full = torch.full((x.shape[0], x.shape[1] + extra, x.shape[2]), float("nan"), device=dev)
+        full[:, :x.shape[1]] = x.detach().to(dev)
+        return full, full[:, :x.shape[1]]
+    (_, qd), (_, kd), (_, vd) = cache(q, 2), cache(k, 3), cache(v, 5)
+    mask_wide = torch.full((bk, tk + 4), float("nan"), device=dev)
+    mask_wide[:, :tk] = mt.to(dev)
+    ctx_full = torch.full((b, tq + 3, d), float("nan"), device=dev)
+    w = torch.full((b, heads, tq, tk), float("nan"), device=dev)
+    ops.sdp_attn_fwd(qd, kd, vd, mask_wide, heads, ctx_full[:, :tq], w, causal, rpk, keep, salt)
+    assert np.abs(w.cpu().numpy() - want_w.detach().numpy()).max() < 2e-6
+    scale = float(want_ctx.detach().abs().max())
+    assert float((ctx_full[:, :tq].cpu() - want_ctx.detach()).abs().max()) < 1e-5 * max(scale, 1.0)
+    assert bool(torch.isnan(ctx_full[:, tq:]).all())
+    if rpk != 1:
+        return
+    g = nrm(b, tq, d)
+    want_ctx.backward(g.double())
+    (_, gd) = cache(g, 1)
+    de = torch.empty((b, heads, tq, tk), device=dev)
+    tol = lambda want: 2e-5 * max(float(want.abs().max()), 1.0)
+    # accumulate=False: NaN-filled gradient caches
+    fulls = [torch.full((x.shape[0], x.shape[1] + e_, d), float("nan"), device=dev) for x, e_ in ((q, 1), (k, 2), (v, 4))]
+    dq, dk, dv = (f[:, :x.shape[1]] for f, x in zip(fulls, (q, k, v)))
+    ops.sdp_attn_bwd(qd, kd, vd, mask_wide, w, gd, heads, dq, dk, dv, de, causal, keep, salt, accumulate=False)
+    for got, full, x in ((dq, fulls[0], q64), (dk, fulls[1], k64), (dv, fulls[2], v64)):
+        assert float((got.cpu().double() - x.grad).abs().max()) < tol(x.grad)
+        assert bool(torch.isnan(full[:, x.shape[1]:]).all())
+    # accumulate=True: onto a non-zero base
+    bases = [nrm(*x.shape) for x in (q, k, v)]
+    fulls = [torch.full((x.shape[0], x.shape[1] + e_, d), float("nan"), device=dev) for x, e_ in ((q, 1), (k, 2), (v, 4))]
+    for f, base in zip(fulls, bases):
+        f[:, :base.shape[1]] = base.to(dev)
+    dq, dk, dv = (f[:, :x.shape[1]] for f, x in zip(fulls, (q, k, v)))
+    ops.sdp_attn_bwd(qd, kd, vd, mask_wide, w, gd, heads, dq, dk, dv, de, causal, keep, salt, accumulate=True)
+    for got, full, x, base in ((dq, fulls[0], q64, bases[0]), (dk, fulls[1], k64, bases[1]), (dv, fulls[2], v64, bases[2])):
+        assert float((got.cpu().double() - (base.double() + x.grad)).abs().max()) < tol(base.double() + x.grad)
+        assert bool(torch.isnan(full[:, x.shape[1]:]).all())
 
 
 @pytest.mark.parametrize("rows,tk,tmax,heads,dh", [(10, 7, 12, 8, 64), (640, 50, 51, 8, 64), (6, 1, 4, 2, 16)])
