@@ -156,6 +156,15 @@ SIGNATURES = {
     "nm_highway_bwd": (I, [P, P, P, L, P, P, P, P, L, P, L, L, I]),
 }
 
+# ... and every symbol include/nmhip_ctc.h declares (the CTC head, csrc/nm_ctc.hip)
+CTC_SIGNATURES = {
+    "nm_ctc_workspace_bytes": (L, [L, L, L]),
+    "nm_ctc_mask_lengths": (I, [P, P, L, L, L, P]),
+    "nm_ctc_loss_fwd": (I, [P, P, L, L, L, L, L, P, L, P, P, I, P, P, P, L]),
+    "nm_ctc_loss_bwd": (I, [P, P, L, L, L, L, L, P, L, P, P, P, P, L, L, P, L]),
+    "nm_ctc_greedy": (I, [P, P, L, L, L, L, L, P, I, ctypes.c_int32, P, P, P, L]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -213,7 +222,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m neuralmonkey_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(CTC_SIGNATURES.items()):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

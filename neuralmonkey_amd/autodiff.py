@@ -977,6 +977,22 @@ def xent(tape: Tape, logits: Var, targets: torch.Tensor, weights: Optional[torch
     return loss_rows
 
 
+def ctc_loss(tape: Tape, logits: Var, bsz: int, steps: int, labels: torch.Tensor, label_len: torch.Tensor,
+             frame_len: torch.Tensor, merge_repeated: bool, grad_scale: Optional[torch.Tensor]):
+    """tf.nn.ctc_loss(ignore_longer_outputs_than_inputs=True) per sentence and summed (decoders/ctc_decoder.py:100-108)
+    over batch-major logits [B*T, K] read as [T, B, K] through their strides (blank = K - 1): (loss [B], sum [1]).
+    When recording, the gradient kernel overwrites the logits with ``grad_scale`` * d sum / d logits, which then *is*
+    the gradient buffer of ``logits`` (as in ``xent``)."""
+    view = logits.data.view(bsz, steps, -1).transpose(0, 1)
+    loss = tape.buf((bsz,))
+    loss_sum = tape.buf((1,))
+    ws = ops.ctc_loss_fwd(view, labels, label_len, frame_len, merge_repeated, loss, loss_sum)
+    if tape.recording:
+        ops.ctc_loss_bwd(view, labels, label_len, frame_len, view, ws, grad_scale)
+        logits.grad = logits.data
+    return loss, loss_sum
+
+
 def conv1d_relu_maxpool(tape: Tape, x: Var, filters: Sequence[Var], biases: Sequence[Var], bsz: int, slen: int,
                         segment: int, mask: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None):
     """encoders/sentence_cnn_encoder.py:113-143: for every filter W_i [w_i, E, n_i] tf.nn.conv1d (stride 1, SAME) +

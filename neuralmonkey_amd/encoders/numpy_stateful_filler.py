@@ -1,6 +1,7 @@
 """Pre-computed feature maps as encoders (mirror of neuralmonkey/encoders/numpy_stateful_filler.py).
 
-``SpatialFiller`` (:155-245) feeds [B,H,W,D] convolutional maps (the captioning configuration:
+``TemporalFiller`` (:82-154) feeds ragged [len, D] feature sequences (speech frames) as the input sequence of a
+``RecurrentEncoder``.  ``SpatialFiller`` (:155-245) feeds [B,H,W,D] convolutional maps (the captioning configuration:
 8x8x2048 ResNet maps, BASELINE configs[3]) to the same Bahdanau attention kernels as a sentence
 encoder; the optional 1x1 convolutions are MFMA GEMMs over the B*H*W positions.  ``output`` is
 the mean over positions (:209-212), computed as a batched [1,S]x[S,D] GEMM.
@@ -13,7 +14,8 @@ import torch
 from .. import autodiff as F
 from .. import ops
 from ..model.model_part import FeedDict, InitializerSpecs, ModelPart
-from ..model.stateful import SpatialStatefulWithOutput, Stateful
+from ..checking import check_argument_types
+from ..model.stateful import SpatialStatefulWithOutput, Stateful, TemporalStateful
 from ..runtime import Placeholder, tensor
 from ..variables import glorot_uniform_initializer, zeros_initializer
 
@@ -101,6 +103,93 @@ class StatefulFiller(ModelPart, Stateful):
             return                                   # the raw vectors: nothing trainable upstream
         ops.ew("copy", d_final, None, tape.grad(var), accumulate=True)
         tape.backward()
+
+
+class TemporalFiller(ModelPart, TemporalStateful):
+    """One pre-computed [len, input_size] array per example as an input sequence (numpy_stateful_filler.py:82-154, the
+    speech features of tests/ctc.ini): ``temporal_states`` is the fed batch, zero-padded to its longest example (capped
+    by ``max_input_len``), ``temporal_mask`` tf.sequence_mask of the kept lengths.  No variables; ``dropout_keep_prob``
+    is stored and, as in the reference, never applied."""
+
+    # pylint: disable=too-many-arguments
+    def __init__(self,
+                 name: str,
+                 data_id: str,
+                 input_size: int,
+                 max_input_len: int = None,
+                 dropout_keep_prob: float = 1.0,
+                 reuse: ModelPart = None,
+                 save_checkpoint: str = None,
+                 load_checkpoint: str = None,
+                 initializers: InitializerSpecs = None) -> None:
+        check_argument_types()
+        ModelPart.__init__(self, name, reuse, save_checkpoint, load_checkpoint, initializers)
+        self.data_id = data_id
+        self.input_size = input_size
+        self.max_input_len = max_input_len
+        self.dropout_keep_prob = dropout_keep_prob
+        self.states_input = Placeholder("{}/temporal_states".format(name))
+        self.lengths_input = Placeholder("{}/encoder_padding_lengths".format(name))
+    # pylint: enable=too-many-arguments
+
+    @property
+    def input_types(self) -> Dict[str, type]:
+        return {self.data_id: np.float32}
+
+    @property
+    def input_shapes(self) -> Dict[str, List]:
+        return {self.data_id: [None, None, self.input_size]}
+
+    @property
+    def dimension(self) -> int:
+        return self.input_size
+
+    def feed_dict(self, dataset, train: bool = False) -> FeedDict:
+        fd = ModelPart.feed_dict(self, dataset, train)
+        series = [np.asarray(x) for x in dataset.get_series(self.data_id)]
+        max_len = max(x.shape[0] for x in series)
+        if self.max_input_len is not None:
+            max_len = min(self.max_input_len, max_len)
+        inputs = np.zeros((len(series), max_len) + series[0].shape[1:], dtype=np.float32)
+        lengths = np.zeros(len(series), dtype=np.int32)
+        for i, x in enumerate(series):
+            lengths[i] = min(max_len, x.shape[0])
+            inputs[i, :lengths[i]] = x[:lengths[i]]
+        fd[self.states_input] = inputs
+        fd[self.lengths_input] = lengths
+        return fd
+
+    @tensor
+    def temporal_states(self, ctx) -> torch.Tensor:
+        """The fed sequences [B, T, input_size] in a persistent device buffer."""
+        fed = ctx.fed(self.states_input)
+        if fed.ndim != 3 or fed.shape[2] != self.input_size:
+            raise ValueError("TemporalFiller '{}': fed sequences of shape {}, expected [batch, time, {}]"
+                             .format(self.name, tuple(fed.shape), self.input_size))
+        return ctx.session.staged((id(self), "states"), ctx.session.to_device(fed, torch.float32, "temporal_states"))
+
+    @tensor
+    def lengths(self, ctx) -> torch.Tensor:
+        return ctx.session.staged((id(self), "len"), ctx.session.to_device(ctx.fed(self.lengths_input), torch.int32,
+                                                                           "len"))
+
+    @tensor
+    def temporal_mask(self, ctx) -> torch.Tensor:
+        steps = ctx.fed(self.states_input).shape[1]
+        return ctx.session.staged((id(self), "mask"), ctx.session.to_device(
+            ctx.fed(self.lengths_input), torch.float32, "mask",
+            lambda lens: (np.arange(steps)[None, :] < np.asarray(lens)[:, None]).astype(np.float32)))
+
+    def stage_inputs(self, ctx) -> None:
+        self.temporal_states(ctx)
+        self.lengths(ctx)
+        self.temporal_mask(ctx)
+
+    def graph_safe_training(self, train_mode: bool) -> bool:
+        return True
+
+    def backward(self, ctx, d_states) -> None:
+        """The fed features: nothing trainable upstream."""
 
 
 class SpatialFiller(ModelPart, SpatialStatefulWithOutput):

@@ -1554,3 +1554,87 @@ def highway_bwd(dy, x, tsave, hsave, dzt, dzh, dx, accumulate_dx=False):
     _lib.check(_lib.load().nm_highway_bwd(_stream(), dy.data_ptr(), x.data_ptr(), ldx, tsave.data_ptr(),
                                           hsave.data_ptr(), dzt.data_ptr(), dzh.data_ptr(), _rc(dzt)[2], dx.data_ptr(),
                                           rows, cols, int(accumulate_dx)), "nm_highway_bwd")
+
+
+# ---- connectionist temporal classification (include/nmhip_ctc.h, csrc/nm_ctc.hip) -------------------------------------
+_CTC_WS = {}
+
+
+def ctc_workspace_bytes(bsz: int, steps: int, max_labels: int) -> int:
+    return int(_lib.load().nm_ctc_workspace_bytes(bsz, steps, max_labels))
+
+
+def ctc_workspace(bsz: int, steps: int, max_labels: int, device) -> torch.Tensor:
+    """Persistent workspace of the CTC calls, one per (device, stream, workspace tag) like the GEMM's split-K slabs; it
+    grows to the largest batch seen.  ``ctc_loss_bwd`` reads what ``ctc_loss_fwd`` left in it."""
+    need = ctc_workspace_bytes(bsz, steps, max_labels)
+    key = (device, _stream(), workspace_tag())
+    ws = _CTC_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        _CTC_WS[key] = ws
+    return ws
+
+
+def _ctc_logits(logits):
+    """logits [T, B, K] as any strided view with a unit class stride (a transposed batch-major product included)."""
+    _f32(logits)
+    assert logits.dim() == 3 and (logits.shape[2] == 1 or logits.stride(2) == 1), "unit class stride"
+    return logits.shape[0], logits.shape[1], logits.shape[2]
+
+
+def ctc_mask_lengths(mask, out=None):
+    """int32 row sums of a 0/1 float mask [B, T] (TemporalStateful.lengths)."""
+    _f32(mask)
+    assert mask.dim() == 2 and (mask.shape[1] == 1 or mask.stride(1) == 1)
+    if out is None:
+        out = torch.empty(mask.shape[0], dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.load().nm_ctc_mask_lengths(_stream(), mask.data_ptr(), mask.stride(0), mask.shape[0], mask.shape[1],
+                                               _i32(out).data_ptr()), "nm_ctc_mask_lengths")
+    return out
+
+
+def ctc_loss_fwd(logits, labels, label_len, frame_len, merge_repeated, loss, loss_sum, workspace=None):
+    """loss [B] and their sum loss_sum [1] of tf.nn.ctc_loss over logits [T, B, K] (blank = K - 1); labels [B, Lmax]
+    int32 with label_len [B] entries each, frame_len [B].  Returns the workspace ``ctc_loss_bwd`` needs."""
+    steps, bsz, k = _ctc_logits(logits)
+    assert labels.dim() == 2 and labels.shape[0] == bsz and (labels.numel() == 0 or labels.is_contiguous())
+    assert label_len.numel() == bsz and frame_len.numel() == bsz and loss.numel() == bsz and loss.is_contiguous()
+    lmax = labels.shape[1]
+    if workspace is None:
+        workspace = ctc_workspace(bsz, steps, lmax, logits.device)
+    _lib.check(_lib.load().nm_ctc_loss_fwd(_stream(), logits.data_ptr(), logits.stride(0), logits.stride(1), steps, bsz, k,
+                                           _i32(labels).data_ptr(), lmax, _i32(label_len).data_ptr(),
+                                           _i32(frame_len).data_ptr(), int(bool(merge_repeated)), _f32(loss).data_ptr(),
+                                           _f32(loss_sum).data_ptr(), workspace.data_ptr(), workspace.numel()),
+               "nm_ctc_loss_fwd")
+    return workspace
+
+
+def ctc_loss_bwd(logits, labels, label_len, frame_len, dlogits, workspace, grad_scale=None):
+    """dlogits = grad_scale[0] * (softmax(logits) - occupancy) after ``ctc_loss_fwd`` on the same operands; dlogits is
+    a [T, B, K] view of its own (strides may differ) or the logits themselves."""
+    steps, bsz, k = _ctc_logits(logits)
+    assert tuple(dlogits.shape) == (steps, bsz, k) and _ctc_logits(dlogits)
+    lmax = labels.shape[1]
+    _lib.check(_lib.load().nm_ctc_loss_bwd(_stream(), logits.data_ptr(), logits.stride(0), logits.stride(1), steps, bsz, k,
+                                           _i32(labels).data_ptr(), lmax, _i32(label_len).data_ptr(),
+                                           _i32(frame_len).data_ptr(), _p(grad_scale), dlogits.data_ptr(),
+                                           dlogits.stride(0), dlogits.stride(1), workspace.data_ptr(), workspace.numel()),
+               "nm_ctc_loss_bwd")
+    return dlogits
+
+
+def ctc_greedy(logits, frame_len, merge_repeated, end_token, tokens, out_len, workspace=None):
+    """tf.nn.ctc_greedy_decoder over logits [T, B, K]: tokens [B, T] int32 = the emitted classes of each sentence, then
+    ``end_token``; out_len [B] = how many were emitted."""
+    steps, bsz, k = _ctc_logits(logits)
+    assert tuple(tokens.shape) == (bsz, steps) and (tokens.numel() == 0 or tokens.is_contiguous())
+    assert out_len.numel() == bsz and frame_len.numel() == bsz
+    if workspace is None:
+        workspace = ctc_workspace(bsz, steps, 0, logits.device)
+    _lib.check(_lib.load().nm_ctc_greedy(_stream(), logits.data_ptr(), logits.stride(0), logits.stride(1), steps, bsz, k,
+                                         _i32(frame_len).data_ptr(), int(bool(merge_repeated)), int(end_token),
+                                         _i32(tokens).data_ptr(), _i32(out_len).data_ptr(), workspace.data_ptr(),
+                                         workspace.numel()), "nm_ctc_greedy")
+    return tokens, out_len
