@@ -496,11 +496,13 @@ def greedy_finish(stats, vocab, finished, sym_out, mask_out, end_id, all_finishe
 
 def beam_topk_step_tiles(logits, stats, b, k, logprob_sum, lengths, finished, penalty, end_id, out_score, out_word,
                          out_beam, out_logprob_sum, out_lengths, out_finished, out_src_row, workspace, rmax, rlse,
-                         all_finished=None):
-    """One beam body from logits whose tile statistics ``logits_stats_gemm`` left in ``stats``."""
+                         all_finished=None, tile=None):
+    """One beam body from logits whose tile statistics ``logits_stats_gemm`` left in ``stats``.  ``tile`` (64 or
+    128) names the width of statistics built elsewhere; by default it is the width ``logits_stats_gemm`` uses."""
     lib = _lib.load()
     assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == b * k
-    tile = lib.nm_logits_stats_tile(b * k)
+    if tile is None:
+        tile = lib.nm_logits_stats_tile(b * k)
     v = logits.shape[1]
     _lib.check(lib.nm_beam_topk_step_tiles(
         _stream(), logits.data_ptr(), logits.stride(0), stats.data_ptr(), tile, b, k, v,

@@ -832,6 +832,7 @@ def test_optimizer_kernels_direct(dev, kind, path):
 HERE = "tests/test_pointwise_kernels_gpu.py::"
 K = "tests/test_kernels_gpu.py::"
 ABI = "tests/test_abi.py::"
+BEAM = "tests/test_beam_kernels_gpu.py::"      # float64 restatement of the beam body (oracle/beam_ref.py)
 LEDGER = {
     # -- contexts, errors, profiler, communicator, test hooks, size queries: no arithmetic kernel
     "nm_last_error": ("no kernel", "thread-local error text"),
@@ -930,7 +931,7 @@ LEDGER = {
     "nm_row_stats": K + "test_row_stats_and_argmax_ties via ops.row_stats",
     "nm_xent": K + "test_xent_fwd_and_grad via ops.xent",
     "nm_xent_colsum": K + "test_xent_with_column_sums via ops.xent_colsum",
-    "nm_beam_topk_step": K + "test_beam_topk_step via ops.beam_topk_step",
+    "nm_beam_topk_step": BEAM + "test_step_against_float64 via ops.beam_topk_step",
     "nm_gather_rows_f32": K + "test_gather_and_token_reorder via ops.gather_rows",
     "nm_beam_reorder_tokens": K + "test_gather_and_token_reorder via ops.beam_reorder_tokens",
     "nm_colsum": K + "test_colsum_both_kernels via ops.colsum",
@@ -943,8 +944,8 @@ LEDGER = {
     "nm_step_group": "tests/test_step_group_gpu.py::test_plain_problems_share_a_launch via ops.StepGroup",
     "nm_decoder_step_fused": "tests/test_step_group_gpu.py::test_decoder_step_fused_is_the_oracle_step via ops.DecoderStepCall",
     "nm_beam_backtrace": "tests/test_beam_fused_gpu.py::test_backtrace_equals_the_per_step_history_gather via ops.beam_backtrace",
-    "nm_beam_topk_step_fused": "tests/test_logits_stats_gpu.py::test_tiles_equal_fused_on_random_rows via ops.beam_topk_step_fused",
-    "nm_beam_topk_step_tiles": "tests/test_logits_stats_gpu.py::test_tiles_equal_fused_on_random_rows via ops.beam_topk_step_tiles",
+    "nm_beam_topk_step_fused": BEAM + "test_step_against_float64 via ops.beam_topk_step_fused",
+    "nm_beam_topk_step_tiles": BEAM + "test_step_against_float64 via ops.beam_topk_step_tiles",
     "nm_greedy_finish": "tests/test_logits_stats_gpu.py::test_greedy_finish_matches_the_reference_update via ops.greedy_finish",
     "nm_logits_stats_gemm": "tests/test_logits_stats_gpu.py::test_stats_gemm_logits_and_merged_statistics via ops.logits_stats_gemm",
     "nm_proj_split_prepare": "tests/test_proj_split_gpu.py::test_split_projection_against_float64_and_the_exact_kernel via ops.proj_split_prepare",
