@@ -165,6 +165,13 @@ CTC_SIGNATURES = {
     "nm_ctc_greedy": (I, [P, P, L, L, L, L, L, P, I, ctypes.c_int32, P, P, P, L]),
 }
 
+# ... and every symbol include/nmhip_label.h declares (the sequence-labelling head, csrc/nm_label.hip)
+LABEL_SIGNATURES = {
+    "nm_label_rows_max_classes": (L, []),
+    "nm_label_rows": (I, [P, P, L, L, L, P, ctypes.c_int32, P, I, P, P, L, P, P, ctypes.c_int32, P]),
+    "nm_label_rows_from_stats": (I, [P, P, L, L, L, P, ctypes.c_int32, P, P, P, P, P, P, ctypes.c_int32, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -222,7 +229,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m neuralmonkey_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(CTC_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
+                              + list(LABEL_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

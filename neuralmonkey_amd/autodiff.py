@@ -977,6 +977,22 @@ def xent(tape: Tape, logits: Var, targets: torch.Tensor, weights: Optional[torch
     return loss_rows
 
 
+def label_xent(tape: Tape, logits: Var, targets: Optional[torch.Tensor], pad_id: int,
+               grad_scale: Optional[torch.Tensor], logprobs: Optional[torch.Tensor] = None,
+               argmax: Optional[torch.Tensor] = None, row_mask: Optional[torch.Tensor] = None, masked_class: int = 0,
+               labels: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Cross entropy per row of a labelling head where the target is not ``pad_id`` (decoders/sequence_labeler.py:
+    122-129), with the log-probabilities / argmax / masked labels of the same rows on request (``ops.label_rows``).
+    When recording, the kernel overwrites the logits with their gradient (scaled by ``grad_scale``), which then *is*
+    the gradient buffer of ``logits`` (as in ``xent``).  ``targets`` None: inference, no loss."""
+    loss_rows = tape.buf((logits.shape[0],)) if targets is not None else None
+    ops.label_rows(logits.data, targets, pad_id, grad_scale, tape.recording and targets is not None, loss_rows, logprobs,
+                   argmax, row_mask, masked_class, labels)
+    if tape.recording and targets is not None:
+        logits.grad = logits.data
+    return loss_rows
+
+
 def ctc_loss(tape: Tape, logits: Var, bsz: int, steps: int, labels: torch.Tensor, label_len: torch.Tensor,
              frame_len: torch.Tensor, merge_repeated: bool, grad_scale: Optional[torch.Tensor]):
     """tf.nn.ctc_loss(ignore_longer_outputs_than_inputs=True) per sentence and summed (decoders/ctc_decoder.py:100-108)

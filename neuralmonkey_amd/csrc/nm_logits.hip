@@ -136,7 +136,7 @@ __global__ __launch_bounds__(NT) void xent_kernel(float* __restrict__ x, long ld
         const float v = xr[c];
         sx += v;
         if (v > bv) { s = s * expf(bv - v) + 1.0f; bv = v; }
-        else s += expf(v - bv);
+        else if (v != -INFINITY) s += expf(v - bv);     // (a -inf class adds nothing; -inf - -inf would be NaN)
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {

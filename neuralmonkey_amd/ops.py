@@ -1640,3 +1640,69 @@ def ctc_greedy(logits, frame_len, merge_repeated, end_token, tokens, out_len, wo
                                          _i32(tokens).data_ptr(), _i32(out_len).data_ptr(), workspace.data_ptr(),
                                          workspace.numel()), "nm_ctc_greedy")
     return tokens, out_len
+
+
+# ---- sequence labelling (include/nmhip_label.h, csrc/nm_label.hip) ----------------------------------------------------
+def label_rows_max_classes() -> int:
+    return int(_lib.load().nm_label_rows_max_classes())
+
+
+def label_rows(logits, targets=None, pad_id=0, grad_scale=None, write_grad=False, loss_rows=None, logprobs=None,
+               argmax=None, row_mask=None, masked_class=0, labels=None):
+    """The rows of a labelling head in one call (decoders/sequence_labeler.py:114-129): ``loss_rows`` [R] = cross
+    entropy where ``targets`` [R] int32 differ from ``pad_id`` (exact zeros elsewhere), ``logprobs`` [R, K] =
+    log_softmax, ``argmax`` [R] int32 (first maximum), ``labels`` [R] int32 = argmax where ``row_mask`` [R] is not zero,
+    else ``masked_class``; with ``write_grad`` the logits [R, K] become grad_scale[0] * d sum(loss) / d logits in
+    place.  One packed kernel up to ``label_rows_max_classes()`` classes; wider rows (an EmbeddingsLabeler over a
+    translation vocabulary) go through the vocabulary-row kernels nm_row_stats / nm_log_softmax / nm_xent, with the
+    same results."""
+    lib = _lib.load()
+    _f32(logits)
+    assert logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1), "unit class stride"
+    rows, k = logits.shape
+    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), k)
+    if write_grad and targets is None:
+        raise ValueError("label_rows: write_grad needs targets")
+    if labels is not None and row_mask is None:
+        raise ValueError("label_rows: labels need a row_mask")
+    for t, n in ((targets, "targets"), (argmax, "argmax"), (labels, "labels")):
+        assert t is None or (_i32(t).numel() == rows and t.is_contiguous()), n
+    for t, n in ((loss_rows, "loss_rows"), (row_mask, "row_mask")):
+        assert t is None or (_f32(t).numel() == rows and t.is_contiguous()), n
+    ldp = 0
+    if logprobs is not None:
+        _f32(logprobs)
+        assert tuple(logprobs.shape) == (rows, k) and (k == 1 or logprobs.stride(1) == 1)
+        ldp = logprobs.stride(0) if rows > 1 else max(logprobs.stride(0), k)
+    if k <= label_rows_max_classes():
+        _lib.check(lib.nm_label_rows(_stream(), logits.data_ptr(), ld, rows, k, _p(targets), int(pad_id), _p(grad_scale),
+                                     int(bool(write_grad)), _p(loss_rows), _p(logprobs), ldp, _p(argmax), _p(row_mask),
+                                     int(masked_class), _p(labels)), "nm_label_rows")
+        return
+    if rows == 0:
+        return
+    if logprobs is not None:                                       # (before anything is launched)
+        x_end = logits.data_ptr() + 4 * ((rows - 1) * ld + k)
+        p_end = logprobs.data_ptr() + 4 * ((rows - 1) * ldp + k)
+        if not (p_end <= logits.data_ptr() or x_end <= logprobs.data_ptr()):         # the packed kernel's range test
+            raise _lib.NMHipError("label_rows: logprobs aliasing logits")
+    dev = logits.device
+    want_stats = logprobs is not None or (targets is not None and loss_rows is not None)
+    rmax = torch.empty(rows, dtype=torch.float32, device=dev) if want_stats else None
+    rlse = torch.empty(rows, dtype=torch.float32, device=dev) if want_stats else None
+    if argmax is None and labels is not None:
+        argmax = torch.empty(rows, dtype=torch.int32, device=dev)
+    if want_stats or argmax is not None:
+        _lib.check(lib.nm_row_stats(_stream(), logits.data_ptr(), ld, rows, k, _p(rmax), _p(rlse), _p(argmax)),
+                   "nm_row_stats")
+    if logprobs is not None:
+        _lib.check(lib.nm_log_softmax(_stream(), logits.data_ptr(), ld, rmax.data_ptr(), rlse.data_ptr(),
+                                      logprobs.data_ptr(), ldp, rows, k), "nm_log_softmax")
+    weights = torch.empty(rows, dtype=torch.float32, device=dev) if write_grad else None
+    if targets is not None or labels is not None:
+        _lib.check(lib.nm_label_rows_from_stats(_stream(), logits.data_ptr(), ld, rows, k, _p(targets), int(pad_id),
+                                                _p(rmax), _p(rlse), _p(loss_rows), _p(weights), _p(argmax), _p(row_mask),
+                                                int(masked_class), _p(labels)), "nm_label_rows_from_stats")
+    if write_grad:            # the gradient alone: the loss above already holds the NaN / exact-zero conventions
+        _lib.check(lib.nm_xent(_stream(), logits.data_ptr(), ld, rows, k, targets.data_ptr(), weights.data_ptr(), None,
+                               _p(grad_scale), 1, 0.0), "nm_xent")
