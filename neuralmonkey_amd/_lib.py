@@ -172,6 +172,15 @@ LABEL_SIGNATURES = {
     "nm_label_rows_from_stats": (I, [P, P, L, L, L, P, ctypes.c_int32, P, P, P, P, P, P, ctypes.c_int32, P]),
 }
 
+# ... and every symbol include/nmhip_pool.h declares (the sentence-level heads, csrc/nm_pool.hip)
+POOL_SIGNATURES = {
+    "nm_pool_fwd": (I, [P, I, P, L, P, L, L, L, P, L, P]),
+    "nm_pool_bwd": (I, [P, I, P, L, P, P, L, P, P, L, L, L, L, P, L, I]),
+    "nm_time_softmax_fwd": (I, [P, P, L, P, L, L, L, P, L, P, L, P]),
+    "nm_time_softmax_bwd": (I, [P, P, L, P, L, P, P, L, L, L, P, L, I]),
+    "nm_sqerr_rows": (I, [P, P, L, L, L, P, P, I, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -230,7 +239,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
-                              + list(LABEL_SIGNATURES.items())):
+                              + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

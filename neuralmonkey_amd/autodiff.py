@@ -1080,3 +1080,57 @@ def highway(tape: Tape, x: Var, w_t: Var, b_t: Var, w_h: Var, b_h: Var) -> Var:
                 tape.defer_bias(g, tape.grad(b))
     tape.record(bwd)
     return out
+
+
+# ---- sentence-level heads (csrc/nm_pool.hip) ------------------------------------------------------------------------------
+def time_softmax(tape: Tape, e: Var, mask: Optional[torch.Tensor], bsz: int, steps: int) -> Var:
+    """[B*T, H] energies -> attention weights normalised along T, masked and renormalised with 1e-8 in the denominator
+    (encoders/attentive.py:60-75), in the energies' own layout."""
+    h = e.shape[1]
+    out = tape.new((bsz * steps, h))
+    s = tape.buf((bsz, steps, h)) if tape.recording else None
+    z = tape.buf((bsz, h)) if tape.recording and mask is not None else None
+    ops.time_softmax_fwd(e.data.view(bsz, steps, h), mask, out.data.view(bsz, steps, h), s, z)
+
+    def bwd():
+        if out.grad is None or not e.needs_grad:
+            return
+        ge, acc = tape.grad_slot(e)
+        ops.time_softmax_bwd(out.grad.view(bsz, steps, h), s, z, mask, ge.view(bsz, steps, h), accumulate=acc)
+    tape.record(bwd)
+    return out
+
+
+def heads_weighted_sum(tape: Tape, w: Var, vals: Var, bsz: int, steps: int) -> Var:
+    """out[b] = w[b]^T . vals[b]: [B*T, H], [B*T, D] -> [B*H, D] (tf.matmul(weights, states, transpose_a=True),
+    encoders/attentive.py:87) -- one batched product on the matrix cores."""
+    h, d = w.shape[1], vals.shape[1]
+    out = tape.new((bsz * h, d))
+    ops.gemm(w.data.view(bsz, steps, h), vals.data.view(bsz, steps, d), out=out.data.view(bsz, h, d), trans_a=True)
+
+    def bwd():
+        if out.grad is None:
+            return
+        dout = out.grad.view(bsz, h, d)
+        if w.needs_grad:                                     # dw[b] = vals[b] . dout[b]^T
+            gw, acc = tape.grad_slot(w)
+            ops.gemm(vals.data.view(bsz, steps, d), dout, out=gw.view(bsz, steps, h), trans_b=True, accumulate=acc)
+        if vals.needs_grad:                                  # dvals[b] = w[b] . dout[b]
+            gv, acc = tape.grad_slot(vals)
+            ops.gemm(w.data.view(bsz, steps, h), dout, out=gv.view(bsz, steps, d), accumulate=acc)
+    tape.record(bwd)
+    return out
+
+
+def squared_error(tape: Tape, pred: Var, targets: Optional[torch.Tensor],
+                  grad_scale: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """Per row sum_k (pred - target)^2 (decoders/sequence_regressor.py:76-79).  When recording, the kernel overwrites
+    the predictions with their gradient (scaled by ``grad_scale``), which then *is* the gradient buffer of ``pred`` (as
+    in ``xent``)."""
+    if targets is None:
+        return None
+    loss_rows = tape.buf((pred.shape[0],))
+    ops.sqerr_rows(pred.data, targets, grad_scale, tape.recording, loss_rows)
+    if tape.recording:
+        pred.grad = pred.data
+    return loss_rows

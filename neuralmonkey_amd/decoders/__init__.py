@@ -3,3 +3,5 @@ from .beam_search_decoder import BeamSearchDecoder       # noqa: F401
 from .transformer import TransformerDecoder             # noqa: F401
 from .ctc_decoder import CTCDecoder                       # noqa: F401
 from .sequence_labeler import EmbeddingsLabeler, SequenceLabeler  # noqa: F401
+from .classifier import Classifier                       # noqa: F401
+from .sequence_regressor import SequenceRegressor        # noqa: F401

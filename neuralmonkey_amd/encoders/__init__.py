@@ -2,3 +2,5 @@ from .recurrent import FactoredEncoder, RecurrentEncoder, SentenceEncoder   # no
 from .numpy_stateful_filler import SpatialFiller, StatefulFiller          # noqa: F401
 from .sentence_cnn_encoder import SentenceCNNEncoder    # noqa: F401
 from .transformer import TransformerEncoder             # noqa: F401
+from .pooling import SequenceAveragePooling, SequenceMaxPooling, SequencePooling    # noqa: F401
+from .attentive import AttentiveEncoder                 # noqa: F401

@@ -188,7 +188,7 @@ class TemporalFiller(ModelPart, TemporalStateful):
     def graph_safe_training(self, train_mode: bool) -> bool:
         return True
 
-    def backward(self, ctx, d_states) -> None:
+    def backward(self, ctx, d_states, d_final=None) -> None:
         """The fed features: nothing trainable upstream."""
 
 

@@ -123,10 +123,11 @@ class EmbeddedFactorSequence(Sequence):
             ops.ew("rowscale", flat, self.temporal_mask(ctx).reshape(-1, 1), flat)
         return out
 
-    def backward(self, ctx, d_states: torch.Tensor) -> None:
+    def backward(self, ctx, d_states: torch.Tensor, d_final=None) -> None:
         """dL/d(temporal_states) [B,S,sum(E)] -> embedding matrix gradients
-        (rows of padded positions carry no gradient: the mask multiply)."""
-        if not self.trainable:
+        (rows of padded positions carry no gradient: the mask multiply).  ``d_final``: the signature every part
+        that ``RunContext.defer_backward`` may call shares; a sequence has no final output."""
+        if not self.trainable or d_states is None:
             return
         ids = self.input_factor_indices(ctx)
         names = self.embedding_matrix_names()

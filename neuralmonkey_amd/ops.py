@@ -1706,3 +1706,109 @@ def label_rows(logits, targets=None, pad_id=0, grad_scale=None, write_grad=False
     if write_grad:            # the gradient alone: the loss above already holds the NaN / exact-zero conventions
         _lib.check(lib.nm_xent(_stream(), logits.data_ptr(), ld, rows, k, targets.data_ptr(), weights.data_ptr(), None,
                                _p(grad_scale), 1, 0.0), "nm_xent")
+
+
+# ---- sentence-level heads (include/nmhip_pool.h, csrc/nm_pool.hip) ------------------------------------------------------
+POOL_MODES = {"max": 0, "avg": 1}
+
+
+def _btd(x, what):
+    """(B, T, D, row stride) of batch-major states [B, T, D] whose (b, t) rows lie one row stride apart."""
+    _f32(x)
+    assert x.dim() == 3, what
+    bsz, steps, d = x.shape
+    assert d == 1 or x.stride(2) == 1, what + ": unit feature stride"
+    ld = x.stride(1) if steps > 1 else max(x.stride(1), d)
+    assert bsz == 1 or x.stride(0) == steps * ld, what + ": batch-major rows one row stride apart"
+    return bsz, steps, d, ld
+
+
+def _ld2(t, cols, what):
+    _f32(t)
+    assert t.dim() == 2 and t.shape[1] == cols and (cols == 1 or t.stride(1) == 1), what
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
+
+
+def pool_fwd(mode, x, mask, out, ties=None):
+    """Masked max / average over time of [B, T, D] states (encoders/pooling.py): ``out`` [B, D]; with "max" also
+    ``ties`` [B, D] int32, how many of the T positions equal the maximum."""
+    bsz, steps, d, ldx = _btd(x, "pool_fwd x")
+    assert tuple(mask.shape) == (bsz, steps) and _f32(mask).is_contiguous()
+    assert out.shape[0] == bsz
+    ldo = _ld2(out, d, "pool_fwd out")
+    if ties is not None:
+        assert tuple(_i32(ties).shape) == (bsz, d) and ties.is_contiguous()
+    _lib.check(_lib.load().nm_pool_fwd(_stream(), POOL_MODES[mode], x.data_ptr(), ldx, mask.data_ptr(), bsz, steps, d,
+                                       out.data_ptr(), ldo, _p(ties)), "nm_pool_fwd")
+    return out
+
+
+def pool_bwd(mode, dout, mask, dx, x=None, out=None, ties=None, accumulate=False):
+    """dx (+)= the gradient of ``pool_fwd``; every (b, t, d) is written, padded positions with exact zeros.  "max" needs
+    ``x``, ``out`` and ``ties`` of the forward call."""
+    bsz, steps, d, lddx = _btd(dx, "pool_bwd dx")
+    assert tuple(mask.shape) == (bsz, steps) and _f32(mask).is_contiguous()
+    assert dout.shape[0] == bsz
+    lddo = _ld2(dout, d, "pool_bwd dout")
+    ldx = ldo = 0
+    if x is not None:
+        assert tuple(x.shape) == (bsz, steps, d)
+        ldx = _btd(x, "pool_bwd x")[3]
+    if out is not None:
+        assert out.shape[0] == bsz
+        ldo = _ld2(out, d, "pool_bwd out")
+    if ties is not None:
+        assert tuple(_i32(ties).shape) == (bsz, d) and ties.is_contiguous()
+    _lib.check(_lib.load().nm_pool_bwd(_stream(), POOL_MODES[mode], _p(x), ldx, mask.data_ptr(), _p(out), ldo, _p(ties),
+                                       dout.data_ptr(), lddo, bsz, steps, d, dx.data_ptr(), lddx, int(bool(accumulate))),
+               "nm_pool_bwd")
+    return dx
+
+
+def time_softmax_fwd(e, mask, w, s_out=None, z_out=None):
+    """encoders/attentive.py:60-75 on energies [B, T, H], normalised along T: w = softmax_t(e) * mask, renormalised with
+    1e-8 in the denominator (mask None: the plain softmax).  ``s_out`` [B, T, H] and ``z_out`` [B, H] are what
+    ``time_softmax_bwd`` reads."""
+    bsz, steps, h, lde = _btd(e, "time_softmax_fwd e")
+    assert tuple(w.shape) == (bsz, steps, h)
+    ldw = _btd(w, "time_softmax_fwd w")[3]
+    lds = 0
+    if s_out is not None:
+        assert tuple(s_out.shape) == (bsz, steps, h)
+        lds = _btd(s_out, "time_softmax_fwd s_out")[3]
+    if mask is not None:
+        assert tuple(mask.shape) == (bsz, steps) and _f32(mask).is_contiguous()
+    if z_out is not None:
+        assert tuple(_f32(z_out).shape) == (bsz, h) and z_out.is_contiguous()
+    _lib.check(_lib.load().nm_time_softmax_fwd(_stream(), e.data_ptr(), lde, _p(mask), bsz, steps, h, w.data_ptr(), ldw,
+                                               _p(s_out), lds, _p(z_out)), "nm_time_softmax_fwd")
+    return w
+
+
+def time_softmax_bwd(dw, s, z, mask, de, accumulate=False):
+    """de (+)= the gradient of ``time_softmax_fwd`` from dw, with s and Z of the forward call."""
+    bsz, steps, h, lddw = _btd(dw, "time_softmax_bwd dw")
+    assert tuple(s.shape) == (bsz, steps, h) and tuple(de.shape) == (bsz, steps, h)
+    lds = _btd(s, "time_softmax_bwd s")[3]
+    ldde = _btd(de, "time_softmax_bwd de")[3]
+    if mask is not None:
+        assert tuple(mask.shape) == (bsz, steps) and _f32(mask).is_contiguous()
+        assert tuple(_f32(z).shape) == (bsz, h) and z.is_contiguous()
+    _lib.check(_lib.load().nm_time_softmax_bwd(_stream(), dw.data_ptr(), lddw, s.data_ptr(), lds, _p(z), _p(mask), bsz,
+                                               steps, h, de.data_ptr(), ldde, int(bool(accumulate))),
+               "nm_time_softmax_bwd")
+    return de
+
+
+def sqerr_rows(pred, targets, grad_scale=None, write_grad=False, loss_rows=None):
+    """decoders/sequence_regressor.py:76-79 per row: ``loss_rows`` [R] = sum_k (pred[r, k] - targets[r])^2; with
+    ``write_grad`` the predictions [R, dim] become grad_scale[0] * 2 (pred - targets) in place."""
+    _f32(pred)
+    assert pred.dim() == 2
+    rows, dim = pred.shape
+    ld = _ld2(pred, dim, "sqerr_rows pred")
+    assert _f32(targets).numel() == rows and targets.is_contiguous()
+    assert loss_rows is None or (_f32(loss_rows).numel() == rows and loss_rows.is_contiguous())
+    _lib.check(_lib.load().nm_sqerr_rows(_stream(), pred.data_ptr(), ld, rows, dim, targets.data_ptr(), _p(grad_scale),
+                                         int(bool(write_grad)), _p(loss_rows)), "nm_sqerr_rows")
+    return loss_rows

@@ -4,3 +4,5 @@ from .plain_runner import PlainRunner                                           
 from .xent_runner import XentRunner                                             # noqa: F401
 from .tensor_runner import RepresentationRunner, TensorRunner                   # noqa: F401
 from .label_runner import LabelRunner                                           # noqa: F401
+from .logits_runner import LogitsRunner                                         # noqa: F401
+from .regression_runner import RegressionRunner                                 # noqa: F401

@@ -140,13 +140,20 @@ class RunContext:
             ops.ew("copy", g.reshape(-1, g.shape[-1]), None, slot[i].view(-1, g.shape[-1]), accumulate=True)
 
     def flush_backward(self) -> None:
-        """Run the deferred encoder backward passes, readers before the encoders they read."""
+        """Run the deferred backward passes, every part exactly once, on the summed gradient, after everything that
+        reads it: a part that another pending part reads -- directly or through parts that are not pending yet (a
+        pooler behind a gradient-reversal view, the recurrent encoder behind that pooler) -- waits for that one's
+        gradient."""
         pending = self.memo.get("pending_backward", {})
+        read_by: Dict[int, set] = {}              # id(part) -> ids of what it reads, transitively: computed once
         while pending:
             order = list(pending)
-            # an encoder that another pending encoder cross-attends to waits for that one's gradient
-            ready = [e for e in order if not any(getattr(o, "input_for_cross_attention", None) is e
-                                                 for o in order if o is not e)]
+            waits = set()
+            for part in order:
+                if id(part) not in read_by:
+                    read_by[id(part)] = _read_by(part)
+                waits |= read_by[id(part)]
+            ready = [e for e in order if id(e) not in waits]
             enc = (ready or order)[0]
             d_states, d_final = pending.pop(enc)[:2]
             if hasattr(enc, "backward"):
@@ -158,6 +165,29 @@ class RunContext:
         fresh masks -- also when the step is a replayed HIP graph."""
         import zlib
         return zlib.crc32("/".join(str(s) for s in site).encode()) & 0xFFFFFFFF
+
+
+def part_reads(part) -> List[Any]:
+    """The model parts whose tensors ``part`` reads in its forward pass, and hands gradients to in its backward pass:
+    its input sequence, the object of a gradient-reversal view, the encoder it cross-attends to."""
+    found = []
+    for attr in ("input_sequence", "_reversed_object", "input_for_cross_attention"):
+        other = getattr(part, attr, None)
+        if other is not None and not any(other is f for f in found):
+            found.append(other)
+    return found
+
+
+def _read_by(part) -> set:
+    """ids of everything ``part`` reads, transitively (itself excluded)."""
+    seen, stack = set(), list(part_reads(part))
+    while stack:
+        other = stack.pop()
+        if id(other) in seen or other is part:
+            continue
+        seen.add(id(other))
+        stack.extend(part_reads(other))
+    return seen
 
 
 _PINNED_FETCH: Dict[Any, list] = {}       # pinned staging buffers of _to_host, by (capacity in elements, dtype)
