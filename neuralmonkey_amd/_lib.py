@@ -181,6 +181,14 @@ POOL_SIGNATURES = {
     "nm_sqerr_rows": (I, [P, P, L, L, L, P, P, I, P]),
 }
 
+# ... and every symbol include/nmhip_convs2s.h declares (the ConvS2S encoder's residual layer, csrc/nm_conv.hip)
+CONVS2S_SIGNATURES = {
+    "nm_conv1d_glu_fwd": (I, [P, P, L, L, L, L, L, P, P, P, L, P, P, I]),
+    "nm_conv1d_glu_workspace_bytes": (L, [L, L, L, L]),
+    "nm_conv1d_glu_bwd": (I, [P, P, L, L, L, L, L, P, P, P, P, L, P, P, L, I, P, P, I, P, L, I]),
+}
+
+
 
 class NMHipError(RuntimeError):
     pass
@@ -239,7 +247,8 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
-                              + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())):
+                              + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
+                              + list(CONVS2S_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -934,6 +934,27 @@ def add_position(tape: Tape, x: Var, signal: torch.Tensor, bsz: int, steps: int,
     return out
 
 
+def add_position_param(tape: Tape, x: Var, table: Var, bsz: int, steps: int) -> Var:
+    """x [B*T, D] + table[:T], the table a trainable [max_length, D] parameter (the order embeddings of
+    encoders/facebook_conv.py:85-100).  Backward: d table[:T] += the sum of the output's gradient over the batch, one
+    column sum over [B, T*D] (nm_colsum: deterministic); rows T.. of the table's gradient are not touched."""
+    d = x.shape[1]
+    assert table.shape[0] >= steps and table.shape[1] == d
+    out = tape.new((bsz * steps, d))
+    ops.add_position(x.data.view(bsz, steps, d), table.data, out.data.view(bsz, steps, d), 0)
+
+    def bwd():
+        if out.grad is None:
+            return
+        if x.needs_grad:
+            gx, acc = tape.grad_slot(x)
+            ops.ew("copy", out.grad, None, gx, accumulate=acc)
+        if table.needs_grad:
+            ops.colsum(out.grad.view(bsz, steps * d), tape.grad(table).view(-1)[:steps * d], accumulate=True)
+    tape.record(bwd)
+    return out
+
+
 def add_row(tape: Tape, x: Var, row: Var) -> Var:
     """x [N, D] + row [1, D] on every row (the target-modality embedding of encoders/transformer.py:202-203);
     the broadcast add is the position-signal kernel with one time step per row."""
@@ -1078,6 +1099,56 @@ def highway(tape: Tape, x: Var, w_t: Var, b_t: Var, w_h: Var, b_h: Var) -> Var:
                 tape.defer_wgrad(xd, g, tape.grad(w), True)
             if b.needs_grad:
                 tape.defer_bias(g, tape.grad(b))
+    tape.record(bwd)
+    return out
+
+
+def conv1d_glu(tape: Tape, x: Var, filt: Var, bias: Var, bsz: int, steps: int) -> Var:
+    """encoders/facebook_conv.py:102-121: glu(tf.nn.conv1d(x, filt [w, C, 2C], 1, "SAME") + bias) + x over x [B*T, C]
+    in ONE launch (nm_conv1d_glu_fwd: the [B, T, 2C] pre-activation stays in registers); a recording tape keeps the
+    linear half and the gate's sigmoid.  Backward: nm_conv1d_glu_bwd -- dx = dy + conv^T(dz), the filter gradient by
+    fixed-order slabs, the bias gradient as column sums."""
+    c = x.shape[1]
+    width = int(filt.shape[0])
+    out = tape.new((bsz * steps, c))
+    lin = tape.buf((bsz * steps, c)) if tape.recording else None
+    sig = tape.buf((bsz * steps, c)) if tape.recording else None
+    x3 = x.data.view(bsz, steps, c)
+    ops.conv1d_glu_fwd(x3, filt.data, bias.data, out.data.view(bsz, steps, c), lin, sig)
+
+    def bwd():
+        if out.grad is None:
+            return
+        dz = tape.buf((bsz * steps, 2 * c))
+        gx, acc = tape.grad_slot(x) if x.needs_grad else (None, False)
+        ws = None
+        if filt.needs_grad:
+            ws = tape.buf((max(1, ops.conv1d_glu_workspace_floats(bsz, steps, c, width)),))
+        ops.conv1d_glu_bwd(x3, filt.data, lin, sig, out.grad.view(bsz, steps, c), dz,
+                           dx=None if gx is None else gx.view(bsz, steps, c), accumulate_dx=acc,
+                           dfilt=tape.grad(filt) if filt.needs_grad else None,
+                           dbias=tape.grad(bias) if bias.needs_grad else None, accumulate_params=True, workspace=ws)
+    tape.record(bwd)
+    return out
+
+
+def time_max(tape: Tape, x: Var, bsz: int, steps: int) -> Var:
+    """tf.reduce_max(x, axis=1) over ALL T positions of x [B*T, D] -> [B, D] (encoders/facebook_conv.py:75-79):
+    nm_pool_fwd(NM_POOL_MAX) under an all-ones mask, which makes its padded-position rule a no-op and leaves max_t x
+    exactly, with the number of positions that hold it.  Backward: nm_pool_bwd splits the gradient evenly over ties, as
+    the gradient of tf.reduce_max does."""
+    d = x.shape[1]
+    out = tape.new((bsz, d))
+    ones = ops.fill(tape.buf((bsz, steps)), 1.0)
+    ties = tape.buf((bsz, d), torch.int32)
+    x3 = x.data.view(bsz, steps, d)
+    ops.pool_fwd("max", x3, ones, out.data, ties)
+
+    def bwd():
+        if out.grad is None or not x.needs_grad:
+            return
+        gx, acc = tape.grad_slot(x)
+        ops.pool_bwd("max", out.grad, ones, gx.view(bsz, steps, d), x=x3, out=out.data, ties=ties, accumulate=acc)
     tape.record(bwd)
     return out
 

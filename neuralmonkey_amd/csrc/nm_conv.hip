@@ -22,6 +22,9 @@
 //                     workgroups into fixed slabs that conv_wgrad_reduce sums in a fixed order: no float atomics,
 //                     repeated runs are bit-identical.
 //   *_generic         scalar kernels for shapes the MFMA path does not take (w > 8, s > 128, > 16 widths).
+//   convs2s_*         the residual layer of the convolutional sequence-to-sequence encoder (facebook_conv.py): the same
+//                     implicit GEMM with a GLU + residual epilogue in registers; its gradients reuse conv_mfma<true>
+//                     and the weight-gradient kernels through conv_grads_launch (further down).
 #include "nm_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -48,7 +51,8 @@ struct ConvArgs {
     const float* x;          // [B, S, E] rows of ldx floats (forward input / weight-gradient input)
     long ldx;
     const float* dz;         // [B, S, ldp] dense pre-activation gradient (backward)
-    float* dx;               // [B, S, E] rows of ldx floats (data gradient)
+    float* dx;               // [B, S, E] rows of lddx floats (data gradient)
+    long lddx;
     int B, S, E, s, Sp, pb;
     int ldp;                 // columns of pooled / argmax / dz (sum of the filter counts)
     int nw;
@@ -158,7 +162,7 @@ __global__ __launch_bounds__(256) void conv_mfma(ConvArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int t = t0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (t < a.S) {
-                    float* p = a.dx + ((long)b * a.S + t) * a.ldx + e;
+                    float* p = a.dx + ((long)b * a.S + t) * a.lddx + e;
                     *p = a.accumulate ? *p + acc[j][r] : acc[j][r];
                 }
             }
@@ -248,7 +252,7 @@ __global__ void conv_bwd_data_generic(ConvArgs a) {
                 for (int f = 0; f < cw.n; ++f) v = fmaf(zr[f], wr[f], v);
             }
         }
-        float* p = a.dx + bt * a.ldx + e;
+        float* p = a.dx + bt * a.lddx + e;
         *p = a.accumulate ? *p + v : v;
     }
 }
@@ -547,6 +551,40 @@ extern "C" int64_t nm_conv1d_wgrad_workspace_bytes(int B, int S, int E, int nw, 
     return slices * slab * (int64_t)sizeof(float);
 }
 
+// The data gradient and the weight gradient of a prepared ConvArgs whose dz is written (x, ldx, dz, dx, lddx, accumulate
+// set): dx (+)= the transposed convolution of every width when a.dx is given; dW_i (+)= the fixed-order slab sums when
+// dW is given (``need`` = nm_conv1d_wgrad_workspace_bytes of the shape).  Shared by nm_conv1d_pool_bwd and
+// nm_conv1d_glu_bwd.
+static void conv_grads_launch(hipStream_t st, ConvArgs& a, bool mfma, float* const* dW, int64_t need, void* workspace,
+                              int accumulate_params) {
+    if (a.dx) {
+        if (mfma)
+            hipLaunchKernelGGL(conv_mfma<true>,
+                               dim3(a.B * ((a.S + CONV_BM - 1) / CONV_BM), (a.E + CONV_BN - 1) / CONV_BN), dim3(256), 0,
+                               st, a);
+        else
+            hipLaunchKernelGGL(conv_bwd_data_generic, dim3(ew_grid((long)a.B * a.S * a.E)), dim3(256), 0, st, a);
+    }
+    if (!dW) return;
+    long slab = 0;
+    int tiles = 0;
+    for (int i = 0; i < a.nw; ++i) {
+        a.wd[i].dW = dW[i];
+        a.wd[i].tile0 = tiles;
+        tiles += a.wd[i].w * ((a.E + WG_BM - 1) / WG_BM) * ((a.wd[i].n + WG_BN - 1) / WG_BN);
+        slab += (long)a.wd[i].w * a.E * a.wd[i].n;
+    }
+    a.ws = static_cast<float*>(workspace);
+    a.ws_slab = slab;
+    a.slices = mfma ? (int)(need / (int64_t)sizeof(float) / slab) : 1;
+    a.tiles_total = tiles;
+    if (mfma)
+        hipLaunchKernelGGL(conv_wgrad_mfma, dim3(tiles, a.slices), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(conv_wgrad_generic, dim3(ew_grid(slab)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(conv_wgrad_reduce, dim3(ew_grid(slab)), dim3(256), 0, st, a, accumulate_params);
+}
+
 extern "C" int nm_conv1d_pool_bwd(void* stream, const float* x, int64_t ldx, int B, int S, int E, int segment,
                                   int nw, const int* widths, const int* counts, const float* const* W,
                                   const float* pooled, const int* argmax, const float* dpooled, int64_t ldp,
@@ -570,39 +608,15 @@ extern "C" int nm_conv1d_pool_bwd(void* stream, const float* x, int64_t ldx, int
     NM_REQUIRE(algo != 1 || fast, "nm_conv1d_pool_bwd: the MFMA kernels take widths <= %d and segments <= %d",
                CONV_FAST_MAX_W, CONV_BM);
     const bool mfma = fast && algo != 2;
-    a.x = x; a.ldx = ldx; a.dz = dz; a.dx = dx; a.accumulate = accumulate_dx;
+    a.x = x; a.ldx = ldx; a.dz = dz; a.dx = dx; a.lddx = ldx; a.accumulate = accumulate_dx;
     hipStream_t st = nm_stream(stream);
     hipLaunchKernelGGL(conv_route_grad, dim3(ew_grid((long)B * a.Sp * a.ldp)), dim3(256), 0, st, dpooled, pooled,
                        argmax, dz, B, S, a.Sp, segment, a.pb, a.ldp);
-    if (dx) {
-        if (mfma)
-            hipLaunchKernelGGL(conv_mfma<true>, dim3(B * ((S + CONV_BM - 1) / CONV_BM), (E + CONV_BN - 1) / CONV_BN),
-                               dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL(conv_bwd_data_generic, dim3(ew_grid((long)B * S * E)), dim3(256), 0, st, a);
-    }
-    if (params) {
-        long slab = 0;
-        int tiles = 0;
-        for (int i = 0; i < nw; ++i) {
-            a.wd[i].dW = dW[i];
-            a.wd[i].bias = dbias[i];
-            a.wd[i].tile0 = tiles;
-            tiles += widths[i] * ((E + WG_BM - 1) / WG_BM) * ((counts[i] + WG_BN - 1) / WG_BN);
-            slab += (long)widths[i] * E * counts[i];
-        }
-        a.ws = static_cast<float*>(workspace);
-        a.ws_slab = slab;
-        a.slices = mfma ? (int)(need / (int64_t)sizeof(float) / slab) : 1;
-        a.tiles_total = tiles;
-        if (mfma)
-            hipLaunchKernelGGL(conv_wgrad_mfma, dim3(tiles, a.slices), dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL(conv_wgrad_generic, dim3(ew_grid(slab)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(conv_wgrad_reduce, dim3(ew_grid(slab)), dim3(256), 0, st, a, accumulate_params);
+    for (int i = 0; params && i < nw; ++i) a.wd[i].bias = dbias[i];
+    conv_grads_launch(st, a, mfma, params ? dW : nullptr, need, workspace, accumulate_params);
+    if (params)
         hipLaunchKernelGGL(conv_bias_grad, dim3((a.ldp + BG_COLS - 1) / BG_COLS), dim3(BG_COLS * BG_LANES), 0, st,
                            dpooled, pooled, B * a.Sp, a.ldp, a, accumulate_params);
-    }
     NM_LAUNCH_CHECK("nm_conv1d_pool_bwd");
 }
 
@@ -627,4 +641,246 @@ extern "C" int nm_highway_bwd(void* stream, const float* dy, const float* x, int
     hipLaunchKernelGGL(highway_bwd_kernel, dim3(ew_grid(rows * cols)), dim3(256), 0, nm_stream(stream), dy, x, tsave,
                        hsave, dzt, dzh, dx, (long)rows, (int)cols, (long)ldx, (long)ldz, accumulate_dx);
     NM_LAUNCH_CHECK("nm_highway_bwd");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// ConvS2S residual layer (include/nmhip_convs2s.h): y = glu(conv1d_SAME(x, W) + bias) + x
+//   encoders/facebook_conv.py:102-121, nn/projection.py:60-75
+// x, y [B, T, C]; W [w, C, 2C]; bias [2C]: output feature c pairs the linear column c with the gate column C + c.
+// ---------------------------------------------------------------------------------------------------------------
+#define GLU_BC 32            // output features per workgroup tile; their gate partners fill the other 32 staged columns
+
+struct GluArgs {
+    const float* x;          // [B, T, C] rows of ldx floats
+    long ldx;
+    const float* W;          // [w, C, 2C]
+    const float* bias;       // [2C]
+    float* y;                // [B, T, C] rows of ldy floats
+    long ldy;
+    float* lin_save;         // [B T, C] contiguous or null
+    float* sig_save;
+    int B, T, C, w;
+};
+
+// one value of the layer from its two pre-activations (bias not yet added); the same expression in both kernels
+__device__ __forceinline__ void glu_store(const GluArgs& a, long row, int c, float lin, float gate) {
+    lin += a.bias[c];
+    const float sig = 1.0f / (1.0f + expf(-(gate + a.bias[a.C + c])));
+    a.y[row * a.ldy + c] = lin * sig + a.x[row * a.ldx + c];
+    if (a.lin_save) {
+        a.lin_save[row * a.C + c] = lin;
+        a.sig_save[row * a.C + c] = sig;
+    }
+}
+
+// Implicit GEMM as conv_mfma<false>: a workgroup owns 128 positions of one sentence x 32 output features; it stages the
+// positions plus the w - 1 halo rows once per chunk of 16 input channels and reads them shifted for every tap.  The 64
+// staged filter columns are the 32 linear columns and their 32 gate partners, so a wave's two accumulators hold the
+// linear and the gate pre-activation of the same (t, c): bias, sigmoid, product, residual add and the optional saves
+// happen in registers, and no [B, T, 2C] pre-activation reaches memory.
+__global__ __launch_bounds__(256) void convs2s_glu_mfma(GluArgs a) {
+    __shared__ __attribute__((aligned(16))) float smem[CONV_CH * CONV_XR + CONV_FAST_MAX_W * CONV_CH * CONV_BN];
+    float (*Xs)[CONV_XR] = reinterpret_cast<float (*)[CONV_XR]>(smem);                       // [ch][row]
+    float (*Ws)[CONV_CH][CONV_BN] = reinterpret_cast<float (*)[CONV_CH][CONV_BN]>(smem + CONV_CH * CONV_XR);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tiles_t = (a.T + CONV_BM - 1) / CONV_BM;
+    const int b = blockIdx.x / tiles_t, t0 = (blockIdx.x % tiles_t) * CONV_BM;
+    const int c0 = blockIdx.y * GLU_BC;
+    const int w = a.w, pad = (w - 1) / 2, C = a.C;
+    const int tstage = t0 - pad, nrows = CONV_BM + w - 1;
+    const long n2 = 2L * C;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+
+    for (int e0 = 0; e0 < C; e0 += CONV_CH) {
+        for (int idx = tid; idx < CONV_CH * nrows; idx += 256) {
+            const int e = idx % CONV_CH, r = idx / CONV_CH;
+            const int t = tstage + r;
+            float v = 0.0f;
+            if (t >= 0 && t < a.T && e0 + e < C) v = a.x[((long)b * a.T + t) * a.ldx + e0 + e];
+            Xs[e][r] = v;
+        }
+        // Ws[k][e][o]: o < 32 the linear column c0 + o, o >= 32 the gate column C + c0 + o - 32
+        for (int idx = tid; idx < w * CONV_CH * CONV_BN; idx += 256) {
+            const int o = idx % CONV_BN, e = (idx / CONV_BN) % CONV_CH, k = idx / (CONV_CH * CONV_BN);
+            const int c = c0 + (o & (GLU_BC - 1));
+            float v = 0.0f;
+            if (e0 + e < C && c < C) v = a.W[((long)k * C + e0 + e) * n2 + (o < GLU_BC ? c : C + c)];
+            Ws[k][e][o] = v;
+        }
+        __syncthreads();
+        const int m = wave * 32 + (lane & 31), kr = lane >> 5;
+        for (int k = 0; k < w; ++k) {
+#pragma unroll
+            for (int cc = 0; cc < CONV_CH; cc += 2) {
+                const float av = Xs[cc + kr][m + k];
+                const float b0 = Ws[k][cc + kr][lane & 31];
+                const float b1 = Ws[k][cc + kr][32 + (lane & 31)];
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1, acc[1], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+
+    // C/D layout of v_mfma_f32_32x32x2_f32: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int c = c0 + (lane & 31);
+    if (c >= C) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int t = t0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (t < a.T) glu_store(a, (long)b * a.T + t, c, acc[0][r], acc[1][r]);
+    }
+}
+
+// scalar kernel: any width
+__global__ void convs2s_glu_generic(GluArgs a) {
+    const long total = (long)a.B * a.T * a.C;
+    const int pad = (a.w - 1) / 2;
+    const long n2 = 2L * a.C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % a.C);
+        const long bt = i / a.C;
+        const int t = (int)(bt % a.T), b = (int)(bt / a.T);
+        float lin = 0.0f, gate = 0.0f;
+        for (int k = 0; k < a.w; ++k) {
+            const int tk = t + k - pad;
+            if (tk < 0 || tk >= a.T) continue;
+            const float* xr = a.x + ((long)b * a.T + tk) * a.ldx;
+            const float* wr = a.W + (long)k * a.C * n2 + c;
+            for (int e = 0; e < a.C; ++e) {
+                lin = fmaf(xr[e], wr[e * n2], lin);
+                gate = fmaf(xr[e], wr[e * n2 + a.C], gate);
+            }
+        }
+        glu_store(a, bt, c, lin, gate);
+    }
+}
+
+// dz[:, :C] = dy sig; dz[:, C:] = dy lin sig (1 - sig); dx (+)= dy, the residual term (dx may be null)
+__global__ void convs2s_glu_dz(const float* __restrict__ dy, long lddy, const float* __restrict__ lin,
+                               const float* __restrict__ sig, float* __restrict__ dz, float* __restrict__ dx, long lddx,
+                               long rows, int C, int accumulate) {
+    const long total = rows * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / C;
+        const int c = (int)(i - r * C);
+        const float g = dy[r * lddy + c], s = sig[i], l = lin[i];
+        dz[r * 2 * C + c] = g * s;
+        dz[r * 2 * C + C + c] = g * l * s * (1.0f - s);
+        if (dx) dx[r * lddx + c] = accumulate ? dx[r * lddx + c] + g : g;
+    }
+}
+
+// dbias (+)= the column sums of dz [rows, cols]: conv_bias_grad's fixed order (16 row lanes, added lane by lane)
+__global__ __launch_bounds__(BG_COLS * BG_LANES) void convs2s_bias_grad(const float* __restrict__ dz, long rows,
+                                                                       int cols, float* dbias, int accumulate) {
+    __shared__ float part[BG_LANES][BG_COLS];
+    const int cl = threadIdx.x % BG_COLS, lane = threadIdx.x / BG_COLS;
+    const int c = blockIdx.x * BG_COLS + cl;
+    float v = 0.0f;
+    if (c < cols)
+        for (long r = lane; r < rows; r += BG_LANES) v += dz[r * cols + c];
+    part[lane][cl] = v;
+    __syncthreads();
+    if (lane != 0 || c >= cols) return;
+    v = 0.0f;
+    for (int l = 0; l < BG_LANES; ++l) v += part[l][cl];
+    dbias[c] = accumulate ? dbias[c] + v : v;
+}
+
+static bool glu_ranges_overlap(const float* p, int64_t ldp, const float* q, int64_t ldq, int64_t rows, int64_t cols) {
+    const float* pe = p + (rows - 1) * ldp + cols;
+    const float* qe = q + (rows - 1) * ldq + cols;
+    return !(pe <= q || qe <= p);
+}
+
+static int glu_check_sizes(const char* who, int64_t B, int64_t T, int64_t C, int64_t w) {
+    NM_REQUIRE(B >= 1 && T >= 1 && C >= 1 && w >= 1, "%s: bad sizes B %lld, T %lld, C %lld, w %lld", who, (long long)B,
+               (long long)T, (long long)C, (long long)w);
+    NM_REQUIRE(B < (1ll << 31) && T < (1ll << 31) && B * T < (1ll << 31), "%s: B*T = %lld rows beyond 2^31", who,
+               (long long)(B * T));
+    NM_REQUIRE(C < (1ll << 30) && w < (1ll << 20) && (C + GLU_BC - 1) / GLU_BC <= NM_MAX_GRID_Y &&
+                   w * ((C + WG_BM - 1) / WG_BM) * ((2 * C + WG_BN - 1) / WG_BN) < (1ll << 31) &&
+                   B * ((T + CONV_BM - 1) / CONV_BM) < (1ll << 31),
+               "%s: grid of %lld x %lld workgroups beyond the launch limits", who,
+               (long long)(B * ((T + CONV_BM - 1) / CONV_BM)), (long long)((C + GLU_BC - 1) / GLU_BC));
+    return NM_OK;
+}
+
+extern "C" int nm_conv1d_glu_fwd(void* stream, const float* x, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t w,
+                                 const float* W, const float* bias, float* y, int64_t ldy, float* lin_save,
+                                 float* sig_save, int algo) {
+    int rc = glu_check_sizes("nm_conv1d_glu_fwd", B, T, C, w);
+    if (rc) return rc;
+    NM_REQUIRE(x && W && bias && y, "nm_conv1d_glu_fwd: null pointer");
+    NM_REQUIRE(ldx >= C, "nm_conv1d_glu_fwd: ldx %lld below C %lld", (long long)ldx, (long long)C);
+    NM_REQUIRE(ldy >= C, "nm_conv1d_glu_fwd: ldy %lld below C %lld", (long long)ldy, (long long)C);
+    NM_REQUIRE(!glu_ranges_overlap(x, ldx, y, ldy, B * T, C),
+               "nm_conv1d_glu_fwd: y aliasing x (a tile reads its neighbours' rows of x as halo)");
+    NM_REQUIRE((lin_save == nullptr) == (sig_save == nullptr),
+               "nm_conv1d_glu_fwd: lin_save and sig_save come together or not at all");
+    NM_REQUIRE(algo >= 0 && algo <= 2, "nm_conv1d_glu_fwd: algo %d (0 auto, 1 mfma, 2 scalar)", algo);
+    NM_REQUIRE(algo != 1 || w <= CONV_FAST_MAX_W, "nm_conv1d_glu_fwd: the MFMA kernel takes widths <= %d, not %lld",
+               CONV_FAST_MAX_W, (long long)w);
+    GluArgs a;
+    a.x = x; a.ldx = ldx; a.W = W; a.bias = bias; a.y = y; a.ldy = ldy; a.lin_save = lin_save; a.sig_save = sig_save;
+    a.B = (int)B; a.T = (int)T; a.C = (int)C; a.w = (int)w;
+    hipStream_t st = nm_stream(stream);
+    if (w <= CONV_FAST_MAX_W && algo != 2)
+        hipLaunchKernelGGL(convs2s_glu_mfma,
+                           dim3((unsigned)(B * ((T + CONV_BM - 1) / CONV_BM)), (unsigned)((C + GLU_BC - 1) / GLU_BC)),
+                           dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(convs2s_glu_generic, dim3(ew_grid(B * T * C)), dim3(256), 0, st, a);
+    NM_LAUNCH_CHECK("nm_conv1d_glu_fwd");
+}
+
+extern "C" int64_t nm_conv1d_glu_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t w) {
+    if (B < 1 || T < 1 || C < 1 || w < 1 || B >= (1ll << 31) || T >= (1ll << 31) || C >= (1ll << 30) || w >= (1ll << 20))
+        return 0;
+    const int width = (int)w, count = (int)(2 * C);
+    return nm_conv1d_wgrad_workspace_bytes((int)B, (int)T, (int)C, 1, &width, &count);
+}
+
+extern "C" int nm_conv1d_glu_bwd(void* stream, const float* x, int64_t ldx, int64_t B, int64_t T, int64_t C, int64_t w,
+                                 const float* W, const float* lin_save, const float* sig_save, const float* dy,
+                                 int64_t lddy, float* dz, float* dx, int64_t lddx, int accumulate_dx, float* dW,
+                                 float* dbias, int accumulate_params, void* workspace, int64_t workspace_bytes,
+                                 int algo) {
+    int rc = glu_check_sizes("nm_conv1d_glu_bwd", B, T, C, w);
+    if (rc) return rc;
+    NM_REQUIRE(x && W && lin_save && sig_save && dy && dz, "nm_conv1d_glu_bwd: null pointer");
+    NM_REQUIRE(ldx >= C, "nm_conv1d_glu_bwd: ldx %lld below C %lld", (long long)ldx, (long long)C);
+    NM_REQUIRE(lddy >= C, "nm_conv1d_glu_bwd: lddy %lld below C %lld", (long long)lddy, (long long)C);
+    NM_REQUIRE(!dx || lddx >= C, "nm_conv1d_glu_bwd: lddx %lld below C %lld", (long long)lddx, (long long)C);
+    NM_REQUIRE(!dx || !glu_ranges_overlap(dx, lddx, dy, lddy, B * T, C), "nm_conv1d_glu_bwd: dx aliasing dy");
+    NM_REQUIRE(algo >= 0 && algo <= 2, "nm_conv1d_glu_bwd: algo %d (0 auto, 1 mfma, 2 scalar)", algo);
+    NM_REQUIRE(algo != 1 || w <= CONV_FAST_MAX_W, "nm_conv1d_glu_bwd: the MFMA kernels take widths <= %d, not %lld",
+               CONV_FAST_MAX_W, (long long)w);
+    const int64_t need = nm_conv1d_glu_workspace_bytes(B, T, C, w);
+    NM_REQUIRE(!dW || workspace, "nm_conv1d_glu_bwd: the weight gradient needs a workspace");
+    NM_REQUIRE(!dW || workspace_bytes >= need, "nm_conv1d_glu_bwd: workspace too small (%lld < %lld bytes)",
+               (long long)workspace_bytes, (long long)need);
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = (int)B; a.S = (int)T; a.E = (int)C; a.s = 1; a.Sp = (int)T; a.pb = 0;
+    a.nw = 1; a.ldp = (int)(2 * C);
+    a.wd[0].W = W; a.wd[0].w = (int)w; a.wd[0].n = (int)(2 * C); a.wd[0].col = 0;
+    a.x = x; a.ldx = ldx; a.dz = dz; a.dx = dx; a.lddx = lddx; a.accumulate = 1;     // onto the residual term
+    const bool mfma = w <= CONV_FAST_MAX_W && algo != 2;
+    hipStream_t st = nm_stream(stream);
+    hipLaunchKernelGGL(convs2s_glu_dz, dim3(ew_grid(B * T * C)), dim3(256), 0, st, dy, (long)lddy, lin_save, sig_save,
+                       dz, dx, (long)lddx, (long)(B * T), (int)C, accumulate_dx);
+    float* const dW_tab[1] = {dW};
+    conv_grads_launch(st, a, mfma, dW ? dW_tab : nullptr, need, workspace, accumulate_params);
+    if (dbias)
+        hipLaunchKernelGGL(convs2s_bias_grad, dim3((unsigned)((2 * C + BG_COLS - 1) / BG_COLS)),
+                           dim3(BG_COLS * BG_LANES), 0, st, dz, (long)(B * T), (int)(2 * C), dbias, accumulate_params);
+    NM_LAUNCH_CHECK("nm_conv1d_glu_bwd");
 }

@@ -1558,6 +1558,55 @@ def highway_bwd(dy, x, tsave, hsave, dzt, dzh, dx, accumulate_dx=False):
                                           rows, cols, int(accumulate_dx)), "nm_highway_bwd")
 
 
+# ---- ConvS2S residual layer (include/nmhip_convs2s.h, csrc/nm_conv.hip) -------------------------------------------------
+def conv1d_glu_workspace_floats(bsz, steps, c, width) -> int:
+    """Floats of the workspace ``conv1d_glu_bwd`` needs for the weight gradient of this shape."""
+    return int(_lib.load().nm_conv1d_glu_workspace_bytes(bsz, steps, c, width)) // 4
+
+
+def conv1d_glu_fwd(x, filt, bias, y, lin_save=None, sig_save=None, algo=0):
+    """y [B, T, C] = glu(conv1d_SAME(x [B, T, C], filt [w, C, 2C]) + bias [2C]) + x in one launch (nm_conv1d_glu_fwd);
+    ``lin_save`` / ``sig_save`` [B*T, C]: what ``conv1d_glu_bwd`` reads, both or neither."""
+    bsz, steps, c, ldx = _btd(x, "conv1d_glu_fwd x")
+    assert tuple(y.shape) == (bsz, steps, c)
+    ldy = _btd(y, "conv1d_glu_fwd y")[3]
+    _f32(filt), _f32(bias)
+    assert filt.dim() == 3 and filt.is_contiguous() and tuple(filt.shape[1:]) == (c, 2 * c), "filter [w, C, 2C]"
+    assert bias.is_contiguous() and bias.numel() == 2 * c
+    for save in (lin_save, sig_save):
+        assert save is None or (_f32(save).is_contiguous() and save.numel() == bsz * steps * c)
+    _lib.check(_lib.load().nm_conv1d_glu_fwd(_stream(), x.data_ptr(), ldx, bsz, steps, c, int(filt.shape[0]),
+                                             filt.data_ptr(), bias.data_ptr(), y.data_ptr(), ldy, _p(lin_save),
+                                             _p(sig_save), int(algo)), "nm_conv1d_glu_fwd")
+    return y
+
+
+def conv1d_glu_bwd(x, filt, lin_save, sig_save, dy, dz, dx=None, accumulate_dx=False, dfilt=None, dbias=None,
+                   accumulate_params=True, workspace=None, algo=0):
+    """The gradient of ``conv1d_glu_fwd``: dz [B*T, 2C] (scratch, written whole); dx (+)= dy + conv^T(dz, filt);
+    dfilt / dbias (+)= the filter / bias gradients (nm_conv1d_glu_bwd; deterministic).  ``workspace``:
+    conv1d_glu_workspace_floats floats, needed with ``dfilt``."""
+    bsz, steps, c, ldx = _btd(x, "conv1d_glu_bwd x")
+    assert tuple(dy.shape) == (bsz, steps, c)
+    lddy = _btd(dy, "conv1d_glu_bwd dy")[3]
+    lddx = 0
+    if dx is not None:
+        assert tuple(dx.shape) == (bsz, steps, c)
+        lddx = _btd(dx, "conv1d_glu_bwd dx")[3]
+    _f32(filt)
+    assert filt.dim() == 3 and filt.is_contiguous() and tuple(filt.shape[1:]) == (c, 2 * c), "filter [w, C, 2C]"
+    assert _f32(dz).is_contiguous() and dz.numel() == bsz * steps * 2 * c
+    assert lin_save.is_contiguous() and sig_save.is_contiguous() and lin_save.numel() == sig_save.numel() == bsz * steps * c
+    assert dfilt is None or (_f32(dfilt).is_contiguous() and dfilt.shape == filt.shape)
+    assert dbias is None or (_f32(dbias).is_contiguous() and dbias.numel() == 2 * c)
+    _lib.check(_lib.load().nm_conv1d_glu_bwd(_stream(), x.data_ptr(), ldx, bsz, steps, c, int(filt.shape[0]),
+                                             filt.data_ptr(), lin_save.data_ptr(), sig_save.data_ptr(), dy.data_ptr(),
+                                             lddy, dz.data_ptr(), _p(dx), lddx, int(bool(accumulate_dx)), _p(dfilt),
+                                             _p(dbias), int(bool(accumulate_params)), _p(workspace),
+                                             0 if workspace is None else workspace.numel() * 4, int(algo)),
+               "nm_conv1d_glu_bwd")
+
+
 # ---- connectionist temporal classification (include/nmhip_ctc.h, csrc/nm_ctc.hip) -------------------------------------
 _CTC_WS = {}
 
