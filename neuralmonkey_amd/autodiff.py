@@ -136,8 +136,23 @@ class Tape:
         self._ops: List[Callable[[], None]] = []
         self._wgrads = {}
         self._chains = {}
+        self._sums: List[Var] = []          # sums that nobody has computed yet (autodiff.add)
         self._n = 0
         self._slot = 0
+
+    def settle(self, written: torch.Tensor) -> None:
+        """``written`` is about to be ADDED TO in place (``add_``, ``linear`` / ``rowscale`` with ``accumulate``): a pending
+        sum (``add``) that reads it is computed first, from the operands as they were when the sum was taken.  Writers
+        that overwrite (``out=`` without ``accumulate``, ``copy(out=)``, ``embedding(out=)``, the ``y_out`` of
+        ``rnn_select``) fill a part of a buffer for the first time -- a recording tape keeps every intermediate -- so a
+        sum taken over that part earlier would have read unwritten memory whenever it was computed: nothing to settle."""
+        if not self._sums:
+            return
+        store = written.untyped_storage().data_ptr()
+        for v in self._sums:
+            if v.pending is not None and any(t.untyped_storage().data_ptr() == store for t in v.pending):
+                v.data                      # pylint: disable=pointless-statement
+        self._sums = [v for v in self._sums if v.pending is not None]
 
     # -- buffers ------------------------------------------------------------------------------
     def rewind(self, slot: int = 0) -> None:
@@ -219,6 +234,7 @@ class Tape:
         for fn in reversed(self._ops):
             fn()
         self._ops = []
+        self._sums = []
         self.flush_wgrads()
 
     # -- weight gradients, grouped -------------------------------------------------------------------------
@@ -307,6 +323,8 @@ def linear(tape: Tape, x: Var, w: Var, b: Optional[Var] = None, out: Optional[Va
         out = tape.new((x.shape[0], n))
     assert act in (None, "relu") or not tape.recording, "of the fused activations only relu has a backward closure"
     assert act is None or not accumulate
+    if accumulate:
+        tape.settle(out._data)              # pylint: disable=protected-access
     ops.gemm(x.data, w.data, out=out.data, bias=None if b is None else b.data, accumulate=accumulate,
              trans_b=trans_b, act=act)
 
@@ -544,6 +562,7 @@ def add(tape: Tape, a: Var, b: Var) -> Var:
     out = tape.new(tuple(a.shape))
     if LAZY_ADD and tape.recording and a.data.is_cuda and a.data.dim() == 2 and a.shape == b.shape:
         out.pending = (a.data, b.data)      # computed by whoever reads it first: a layer norm does it on the way
+        tape._sums.append(out)              # pylint: disable=protected-access
     else:
         ops.ew("add", a.data, b.data, out.data)
 
@@ -567,6 +586,7 @@ def add(tape: Tape, a: Var, b: Var) -> Var:
 
 def add_(tape: Tape, acc: Var, x: Var) -> Var:
     """acc += x in place (a sum needs none of its inputs in the backward pass)."""
+    tape.settle(acc._data)                  # pylint: disable=protected-access
     ops.ew("copy", x.data, None, acc.data, accumulate=True)
 
     def bwd():
@@ -826,6 +846,8 @@ def rowscale(tape: Tape, x: Var, s: Var, out: Optional[Var] = None, accumulate: 
     if out is None:
         assert not accumulate
         out = tape.new(tuple(x.shape))
+    if accumulate:
+        tape.settle(out._data)              # pylint: disable=protected-access
     ops.ew("rowscale", x.data, s.data, out.data, accumulate=accumulate)
 
     def bwd():
