@@ -360,10 +360,12 @@ def lstm_cell(tape: Tape, z: Var, c_prev: Var, forget_bias: float = 1.0):
     def bwd():
         if h_new.grad is None and c_new.grad is None:
             return
+        if not z.needs_grad and not c_prev.needs_grad:
+            return
         dz, acc_z = tape.grad_slot(z)
         dcp, acc_c = tape.grad_slot(c_prev)
-        if dz is None:
-            return
+        if dz is None:                      # only c_prev takes a gradient: the kernel still writes dz somewhere
+            dz = tape.buf((rows, 4 * h))
         ops.lstm_cell_bwd(h_new.grad, c_new.grad, gates, c_prev.data, c_new.data, dz, dcp, acc_z, acc_c)
     tape.record(bwd)
     return h_new, c_new
@@ -381,12 +383,14 @@ def nematus_cell(tape: Tape, g_pre: Var, sc: Var, ci: Var, h_prev: Var) -> Var:
     def bwd():
         if h_new.grad is None:
             return
+        if not (g_pre.needs_grad or ci.needs_grad or sc.needs_grad or h_prev.needs_grad):
+            return
         dg, acc_g = tape.grad_slot(g_pre)
         dci, acc_ci = tape.grad_slot(ci)
         dsc, acc_sc = tape.grad_slot(sc)
         dhp, acc_hp = tape.grad_slot(h_prev)
-        if dg is None:
-            return
+        if dg is None:                      # the gates take no gradient, somebody else does: the kernel still writes dg
+            dg = tape.buf((rows, 2 * h))
         ops.nematus_cell_bwd(h_new.grad, ru, c, sc.data, h_prev.data, dg, dci, dsc, dhp, acc_g, acc_ci, acc_sc, acc_hp)
     tape.record(bwd)
     return h_new
@@ -889,7 +893,7 @@ def attn_energies(tape: Tape, y: Var, hf: Var, v: Var, bsz: int, slen: int, rows
         if y.needs_grad:
             ops.ew("copy", dy, None, tape.grad(y), accumulate=True)
         if v.needs_grad:
-            ops.colsum(dvp, v.grad.view(-1), accumulate=True)
+            ops.colsum(dvp, tape.grad(v).view(-1), accumulate=True)
     tape.record(bwd)
     return out
 

@@ -13,6 +13,12 @@ Inputs are ``(kind, array)``:
   "const"  tape.leaf(data, needs_grad=False): nothing may be allocated or written for it;
   "aux"    a plain tensor (ids, lengths, masks, position signals).
 
+Where a tape function's signature needs plumbing that a graph description should not repeat, ``TapeNS`` has an adapter
+and ``RefNS`` a mirror of the same signature: the merged NematusGRU step takes the four kernels and four biases
+({"gi", "ci", "gs", "cs"} -> (kernel, bias or None)) and the adapter concatenates them as nn/cells.py does;
+``f.tensor`` is a tensor of the caller's (None in the reference); ``f.exact(name, t)`` names a side result that is no
+``Var`` and is compared bit for bit.
+
 With NM_TAPE_STATS=<path> in the environment the largest e32 / max|f64| and the largest GPU error / bound seen under each
 label (``STATS``) are written to that file as JSON when the process ends: the figures a pull request reports.
 """
@@ -95,6 +101,8 @@ class TapeNS:
         self.F = autodiff
         self.tape = tape
         self.masks = []             # of every dropout call, in order: where the forward output is not zero
+        self.exacts = {}            # name -> side result compared bit for bit (``exact``)
+        self.routes = []            # the forward route of every nematus_cell_merged call that named one
 
     def __getattr__(self, name):
         fn = getattr(self.F, name)
@@ -117,6 +125,61 @@ class TapeNS:
     def sdp_attention(self, q, k, v, mask, heads, b, tq, tk):
         return self.F.sdp_attention(self.tape, q, k, v, mask, heads, b, tq, b, tk)
 
+    def exact(self, name, t):
+        """A side result that is no ``Var`` (a pooled mask, pooled lengths): compared with the reference's bit for bit."""
+        self.exacts[name] = t.detach().cpu().double()
+
+    def tensor(self, shape):
+        """A tensor of the caller's (``w_out=``): poisoned like every other buffer."""
+        return torch.full(tuple(shape), float("nan"), device=self.tape.ctx.device)
+
+    def attn_softmax(self, e, mask, bsz, rows_per_key=1, w_out=None):
+        w = self.F.attn_softmax(self.tape, e, mask, bsz, rows_per_key, w_out)
+        if w_out is not None:
+            assert w.data.data_ptr() == w_out.data_ptr(), "attn_softmax did not write the caller's tensor"
+        return w
+
+    def _merged(self, p):
+        """What nn/cells.py keeps per run context: [W_gi | W_ci], [W_gs | W_cs] and the concatenated biases."""
+        def cat(a, b, dim):
+            kernels = [p[a][0].data, p[b][0].data]
+            biases = None if p[a][1] is None else torch.cat([p[a][1].data.reshape(-1), p[b][1].data.reshape(-1)])
+            return torch.cat(kernels, dim).contiguous(), biases
+        return cat("gi", "ci", 1) + cat("gs", "cs", 1)
+
+    def nematus_input_projection(self, x_all, p):
+        w_in, b_in, _, _ = self._merged(p)
+        return self.F.nematus_input_projection(self.tape, x_all, w_in, b_in, p)
+
+    def nematus_cell_merged(self, x, h_prev, p, x_proj=None, out=None, route=None):
+        """``route``: the forward route the case's shapes select ("full", "state" or "unfused").  Asserted twice: from
+        ``ops.nematus_state_step_ok`` / ``nematus_full_step_ok`` on the very tensors, and from the launch that ran (with
+        a module switch off: the next route down)."""
+        from neuralmonkey_amd import ops
+        w_in, b_in, w_st, b_st = self._merged(p)
+        names = ("nematus_full_step", "nematus_state_step", "nematus_cell_fwd")
+        saved = {n: getattr(ops, n) for n in names}
+        ran = []
+        for n in names:
+            setattr(ops, n, lambda *a, _n=n, **k: (ran.append(_n), saved[_n](*a, **k))[1])
+        try:
+            h_new = self.F.nematus_cell_merged(self.tape, x, h_prev, w_in, b_in, w_st, b_st, p, x_proj=x_proj, out=out)
+        finally:
+            for n in names:
+                setattr(ops, n, saved[n])
+        if route is not None:
+            state_ok = ops.nematus_state_step_ok(h_prev.data, w_st, h_new.data)
+            full_ok = state_ok and x_proj is None and ops.nematus_full_step_ok(x.data, w_in)
+            assert ("full" if full_ok else "state" if state_ok else "unfused") == route, (route, state_ok, full_ok)
+            if route == "full" and not self.F.FUSED_FULL_STEP:
+                route = "state"
+            if route != "unfused" and not self.F.FUSED_STATE_STEP:
+                route = "unfused"
+            want = {"full": "nematus_full_step", "state": "nematus_state_step", "unfused": "nematus_cell_fwd"}[route]
+            assert ran == [want], (ran, want)
+            self.routes.append(route)
+        return h_new
+
 
 class RefNS:
     """The same functions over torch tensors of one dtype, differentiable by autograd."""
@@ -124,6 +187,7 @@ class RefNS:
     def __init__(self, dtype, masks=None):
         self.dtype = dtype
         self.masks = masks
+        self.exacts = {}
         self._n_drop = 0
 
     def _aux(self, t):
@@ -269,6 +333,75 @@ class RefNS:
     def time_sum(self, x, bsz, steps):
         return x.view(bsz, steps, -1).sum(1)
 
+    def exact(self, name, t):
+        self.exacts[name] = t.detach().double()
+
+    def tensor(self, shape):             # pylint: disable=unused-argument
+        return None
+
+    def lstm_cell(self, z, c_prev, forget_bias=1.0):
+        from oracle import pointwise_ref as P
+        c_new, h_new, _ = P.lstm_cell(z, c_prev, forget_bias)
+        return h_new, c_new
+
+    def nematus_cell(self, g_pre, sc, ci, h_prev):
+        from oracle import pointwise_ref as P
+        return P.nematus_cell(g_pre, sc, ci, h_prev)[0]
+
+    @staticmethod
+    def _product(x, wb):
+        w, b = wb
+        return x @ w if b is None else x @ w + b.reshape(1, -1)
+
+    def nematus_input_projection(self, x_all, p):
+        return torch.cat([self._product(x_all, p["gi"]), self._product(x_all, p["ci"])], 1)
+
+    def nematus_cell_merged(self, x, h_prev, p, x_proj=None, out=None, route=None):      # pylint: disable=unused-argument
+        """The step from the four kernels and four biases themselves (nn/ortho_gru_cell.py:73-105), so that autograd
+        yields THEIR gradients.  With ``out=`` the result is copied into the caller's rows and the chain goes on with
+        the result itself (a later write into other rows of that buffer must not invalidate what autograd saved)."""
+        h = h_prev.shape[1]
+        xp = x_proj if x_proj is not None else self.nematus_input_projection(x, p)
+        gates = torch.sigmoid(xp[:, :2 * h] + self._product(h_prev, p["gs"]))
+        r, u = gates[:, :h], gates[:, h:]
+        cand = torch.tanh(xp[:, 2 * h:] + r * self._product(h_prev, p["cs"]))
+        y = u * h_prev + (1 - u) * cand
+        if out is not None:
+            out.copy_(y)
+        return y
+
+    def attn_energies(self, y, hf, v, bsz, slen, rows_per_key=1):
+        a = y.shape[1]
+        pre = y.view(bsz, rows_per_key, 1, a) + hf.view(bsz, 1, slen, a)
+        return (torch.tanh(pre) * v.reshape(-1)).sum(-1).reshape(bsz * rows_per_key, slen)
+
+    def attn_softmax(self, e, mask, bsz, rows_per_key=1, w_out=None):                   # pylint: disable=unused-argument
+        from oracle import pointwise_ref as P
+        if mask is None:
+            return torch.softmax(e, -1)
+        return P.attn_softmax(e, P.mask_rows(self._aux(mask), e.shape[0], bsz, rows_per_key))
+
+    def time_softmax(self, e, mask, bsz, steps):
+        """tests/pool_ref.py::time_softmax in torch: softmax over T, times the mask, divided by (sum + 1e-8)."""
+        h = e.shape[1]
+        w = torch.softmax(e.view(bsz, steps, h), 1)
+        if mask is not None:
+            u = w * self._aux(mask)[:, :, None]
+            w = u / (u.sum(1, keepdim=True) + 1e-8)
+        return w.reshape(bsz * steps, h)
+
+    def heads_weighted_sum(self, w, vals, bsz, steps):
+        h, d = w.shape[1], vals.shape[1]
+        return (w.view(bsz, steps, h).transpose(1, 2) @ vals.view(bsz, steps, d)).reshape(bsz * h, d)
+
+    def conv1d_relu_maxpool(self, x, filters, biases, bsz, slen, segment, mask=None, lengths=None):
+        from . import sent_cnn_ref as C
+        x3 = x.view(bsz, slen, -1)
+        pooled = torch.cat([C.same_max_pool(C.conv_relu(x3, w, b), segment) for w, b in zip(filters, biases)], 1)
+        pmask = None if mask is None else C.same_max_pool(self._aux(mask)[:, None, :], segment)[:, 0]
+        plens = None if lengths is None else (self._aux(lengths) + segment - 1) // segment
+        return pooled.transpose(1, 2).reshape(-1, pooled.shape[1]), pmask, plens
+
 
 # ------------------------------------------------------------------------------------------------ one graph, three times
 class Case:
@@ -338,7 +471,7 @@ def run_tape(dev, case, ctx=None, key="tape_ref", recording=True, backward=True)
             run.vars[name] = tape.leaf(data, needs_grad=(kind == "leaf"))
     ns = TapeNS(tape)
     run.outs = outs = case.build(ns, types.SimpleNamespace(**run.vars))
-    run.masks = ns.masks
+    run.masks, run.exacts, run.routes = ns.masks, ns.exacts, ns.routes
     names = case.values if case.values is not None else list(outs)
     run.values = {n: outs[n].data.detach().cpu().clone() for n in names}
     run.grads = {}
@@ -358,17 +491,23 @@ def run_tape(dev, case, ctx=None, key="tape_ref", recording=True, backward=True)
             if kind == "const":
                 assert g is None, "a gradient buffer for {}, which needs none".format(name)
             run.grads[name] = None if g is None else g.detach().cpu().clone()
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as err:            # a device fault: nothing more may run on this GPU in this session
-        import pytest
-        pytest.exit("device error in {}: {}".format(case.name, err), returncode=3)
+    sync(case.name)
     return run
 
 
-def run_ref(case, dtype, masks=None):
+def sync(what):
+    """Wait for the device; a device error ends the pytest run: nothing more may run on this GPU in this session."""
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as err:
+        import pytest
+        pytest.exit("device error in {}: {}".format(what, err), returncode=3)
+
+
+def run_ref(case, dtype, masks=None, exacts=None):
     """-> (values, grads, pure): ``grads`` of a "param" is base + gradient computed in ``dtype``; ``pure`` the gradient
-    alone (where it is exactly zero nobody touched the buffer)."""
+    alone (where it is exactly zero nobody touched the buffer).  ``exacts``: a dict that receives the side results the
+    graph named with ``f.exact``.  A case in which no output receives a gradient has zero gradients."""
     leaves, handles = {}, {}
     for name, (kind, arr) in case.inputs.items():
         if kind == "aux":
@@ -379,7 +518,10 @@ def run_ref(case, dtype, masks=None):
             t.requires_grad_(True)
             leaves[name] = t
         handles[name] = t
-    outs = case.build(RefNS(dtype, masks), types.SimpleNamespace(**handles))
+    ns = RefNS(dtype, masks)
+    outs = case.build(ns, types.SimpleNamespace(**handles))
+    if exacts is not None:
+        exacts.update(ns.exacts)
     names = case.values if case.values is not None else list(outs)
     values = {n: outs[n].detach().clone() for n in names}
     loss = None
@@ -388,7 +530,7 @@ def run_ref(case, dtype, masks=None):
         if g is not None:
             term = (o * g.to(dtype)).sum()
             loss = term if loss is None else loss + term
-    got = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
+    got = [None] * len(leaves) if loss is None else torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
     grads, pure = {}, {}
     for (name, t), g in zip(leaves.items(), got):
         g = torch.zeros_like(t) if g is None else g
@@ -400,7 +542,8 @@ def run_ref(case, dtype, masks=None):
 class Refs:
     def __init__(self, case, masks=None):
         self.masks = masks
-        self.v64, self.g64, self.pure = run_ref(case, torch.float64, masks)
+        self.exacts = {}
+        self.v64, self.g64, self.pure = run_ref(case, torch.float64, masks, self.exacts)
         self.v32, self.g32, _ = run_ref(case, torch.float32, masks)
 
 
@@ -438,11 +581,19 @@ def close(label, name, got, w64, w32):
         label, name, err, bound, float((w32.double() - w64).abs().max()))
 
 
+def check_values(label, run, refs):
+    """The values of the tape run against float64 under the per-tensor bound, the side results bit for bit."""
+    for n, got in run.values.items():
+        close(label, "value " + n, got, refs.v64[n], refs.v32[n])
+    assert set(run.exacts) == set(refs.exacts), (label, sorted(run.exacts), sorted(refs.exacts))
+    for n, got in run.exacts.items():
+        assert torch.equal(got, refs.exacts[n]), "{} / {}: {} instead of {}".format(label, n, got, refs.exacts[n])
+
+
 def check(label, case, run, refs):
     """Every value and gradient of the tape run against float64 under the per-tensor bound; what float64 leaves exactly
     zero (rows nobody touched) must be exactly the base, or exactly zero, on the tape."""
-    for n, got in run.values.items():
-        close(label, "value " + n, got, refs.v64[n], refs.v32[n])
+    check_values(label, run, refs)
     for n, w64 in refs.g64.items():
         got = run.grads[n]
         kind = case.inputs[n][0]
@@ -488,5 +639,5 @@ def run_all_settings(dev, monkeypatch, case, label=None):
         try:
             check(label, case, run, refs)
         except AssertionError as err:
-            raise AssertionError("[{} off] {}".format(name, err)) from err
+            raise AssertionError("[{}, {} off] {}".format(case.name, name, err)) from err
     return refs

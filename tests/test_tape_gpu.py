@@ -10,7 +10,9 @@ the helper asserts that this bound stays within 1e-4 x max(max|f64|, 1) (``test_
 so on the host for every graph), so no graph passes by widening its own bound.  Each graph runs with every module
 switch on and with each one off in turn.
 
-``TAPE_TESTS`` says for every tape function what runs it: a test here, a test elsewhere, or the model tests only.
+``TAPE_TESTS`` says for every tape function which test runs it on a ``Tape``: a test here or a test elsewhere (the fused
+cells, the attention pieces, the sentence heads, the convolution, the losses and the parameter lookups:
+tests/test_tape_functions_gpu.py).  No function is left to the model tests alone.
 """
 import inspect
 import itertools
@@ -463,14 +465,14 @@ def test_arena_and_inference_graphs_are_well_conditioned():
 
 
 # every public function of autodiff that takes a tape, and every public method of Tape: the test of THIS module that
-# runs it, the node id of a test elsewhere that runs it on a Tape, or "model tests only: <file>"
+# runs it, or the node id of a test elsewhere that runs it on a Tape
 TAPE_TESTS = {
     "Tape.rewind": "test_inference_tape_reuses_two_slots",
     "Tape.buf": "test_zero_arena_rolls_over_and_forgets_the_previous_step",
     "Tape.new": "test_linear_paths",
     "Tape.leaf": "test_fanout_overwrites_once_then_accumulates",
-    "Tape.param": "model tests only: tests/test_transformer_gpu.py",
-    "Tape.named_param": "model tests only: tests/test_transformer_gpu.py",
+    "Tape.param": "tests/test_tape_functions_gpu.py::test_param_and_named_param_are_slices_of_the_flat_gradient",
+    "Tape.named_param": "tests/test_tape_functions_gpu.py::test_param_and_named_param_are_slices_of_the_flat_gradient",
     "Tape.grad": "test_fanout_overwrites_once_then_accumulates",
     "Tape.grad_slot": "test_fanout_overwrites_once_then_accumulates",
     "Tape.view": "test_fanout_overwrites_once_then_accumulates",
@@ -515,17 +517,17 @@ TAPE_TESTS = {
     "time_max": "tests/test_convs2s_kernels_gpu.py::test_taped_encoder_functions_match_float64_autograd",
     "ctc_loss": "tests/test_ctc_kernels_gpu.py::test_autodiff_op_overwrites_the_logits_with_their_gradient",
     "label_xent": "tests/test_label_kernels_gpu.py::test_autodiff_op_overwrites_the_logits_with_their_gradient",
-    "lstm_cell": "model tests only: tests/test_general_gpu.py",
-    "nematus_cell": "model tests only: tests/test_general_gpu.py",
-    "nematus_input_projection": "model tests only: tests/test_general_gpu.py",
-    "nematus_cell_merged": "model tests only: tests/test_general_gpu.py",
-    "attn_energies": "model tests only: tests/test_multisource_gpu.py",
-    "attn_softmax": "model tests only: tests/test_general_gpu.py",
-    "xent": "model tests only: tests/test_general_gpu.py",
-    "squared_error": "model tests only: tests/test_classifier_gpu.py",
-    "conv1d_relu_maxpool": "model tests only: tests/test_sentence_cnn_encoder_gpu.py",
-    "time_softmax": "model tests only: tests/test_classifier_gpu.py",
-    "heads_weighted_sum": "model tests only: tests/test_classifier_gpu.py",
+    "lstm_cell": "tests/test_tape_functions_gpu.py::test_lstm_cell",
+    "nematus_cell": "tests/test_tape_functions_gpu.py::test_nematus_cell",
+    "nematus_input_projection": "tests/test_tape_functions_gpu.py::test_nematus_cell_merged",
+    "nematus_cell_merged": "tests/test_tape_functions_gpu.py::test_nematus_cell_merged",
+    "attn_energies": "tests/test_tape_functions_gpu.py::test_attn_energies",
+    "attn_softmax": "tests/test_tape_functions_gpu.py::test_attn_softmax",
+    "xent": "tests/test_tape_functions_gpu.py::test_xent_overwrites_the_logits_with_their_gradient",
+    "squared_error": "tests/test_tape_functions_gpu.py::test_squared_error_overwrites_the_predictions_with_their_gradient",
+    "conv1d_relu_maxpool": "tests/test_tape_functions_gpu.py::test_conv1d_relu_maxpool",
+    "time_softmax": "tests/test_tape_functions_gpu.py::test_sentence_heads",
+    "heads_weighted_sum": "tests/test_tape_functions_gpu.py::test_sentence_heads",
 }
 
 
@@ -545,10 +547,10 @@ def test_every_tape_function_is_in_the_registry():
     assert names == set(TAPE_TESTS), (sorted(names - set(TAPE_TESTS)), sorted(set(TAPE_TESTS) - names))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for name, where in TAPE_TESTS.items():
-        if where.startswith("model tests only: "):
-            assert os.path.isfile(os.path.join(root, where[len("model tests only: "):])), (name, where)
-        elif "::" in where:
+        assert not where.startswith("model tests only"), (name, where)
+        if "::" in where:
             path, test = where.split("::")
+            assert os.path.isfile(os.path.join(root, path)), (name, where)
             module = importlib.import_module(path[:-3].replace("/", "."))
             assert callable(getattr(module, test)), (name, where)
         else:
