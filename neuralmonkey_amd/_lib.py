@@ -188,6 +188,17 @@ CONVS2S_SIGNATURES = {
     "nm_conv1d_glu_bwd": (I, [P, P, L, L, L, L, L, P, P, P, P, L, P, P, L, I, P, P, I, P, L, I]),
 }
 
+# ... and every symbol include/nmhip_image.h declares (the image stack of CNNEncoder, csrc/nm_image.hip)
+IMAGE_SIGNATURES = {
+    "nm_conv2d_fwd": (I, [P, P, L, L, L, L, L, P, L, L, I, P, P, L, I]),
+    "nm_conv2d_workspace_bytes": (L, [L, L, L, L, L, L, I]),
+    "nm_conv2d_bwd": (I, [P, P, L, L, L, L, L, P, L, L, I, P, L, P, L, I, P, P, I, P, L, I]),
+    "nm_bn2d_fwd": (I, [P, P, L, L, L, P, P, F, F, I, I, P, P, P, P, P, L]),
+    "nm_bn2d_bwd": (I, [P, P, L, P, L, P, L, L, L, P, P, P, F, I, P, L, I, P, P, I, P]),
+    "nm_window2d_fwd": (I, [P, P, L, L, L, L, L, L, L, L, L, I, I, P, L, P]),
+    "nm_window2d_bwd": (I, [P, P, L, P, L, L, L, L, L, L, L, L, I, I, P, L, I]),
+    "nm_map_columns": (I, [P, P, P, L, L, L, L, I]),
+}
 
 
 class NMHipError(RuntimeError):
@@ -248,7 +259,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
                               + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
-                              + list(CONVS2S_SIGNATURES.items())):
+                              + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -4,3 +4,4 @@ from .sentence_cnn_encoder import SentenceCNNEncoder    # noqa: F401
 from .transformer import TransformerEncoder             # noqa: F401
 from .pooling import SequenceAveragePooling, SequenceMaxPooling, SequencePooling    # noqa: F401
 from .attentive import AttentiveEncoder                 # noqa: F401
+from .cnn_encoder import CNNEncoder, CNNTemporalView     # noqa: F401

@@ -1861,3 +1861,147 @@ def sqerr_rows(pred, targets, grad_scale=None, write_grad=False, loss_rows=None)
     _lib.check(_lib.load().nm_sqerr_rows(_stream(), pred.data_ptr(), ld, rows, dim, targets.data_ptr(), _p(grad_scale),
                                          int(bool(write_grad)), _p(loss_rows)), "nm_sqerr_rows")
     return loss_rows
+
+
+# ---- the image stack (include/nmhip_image.h, csrc/nm_image.hip) ------------------------------------------------------------
+PADDINGS = {"valid": 0, "same": 1}
+WINDOW_MODES = {"max": 0, "avg": 1}
+BN_EPSILON = 1e-3           # tf.layers.batch_normalization's defaults (encoders/cnn_encoder.py:107)
+BN_MOMENTUM = 0.99
+
+
+def _nhwc(x, what):
+    """(B, H, W, C, row stride) of an NHWC map whose (b, y, x) rows lie one row stride apart."""
+    _f32(x)
+    assert x.dim() == 4, what
+    bsz, h, w, c = x.shape
+    assert c == 1 or x.stride(3) == 1, what + ": unit channel stride"
+    ld = x.stride(2) if w > 1 else max(x.stride(2), c)
+    assert (h == 1 or x.stride(1) == w * ld) and (bsz == 1 or x.stride(0) == h * w * ld), what + ": rows one stride apart"
+    return bsz, h, w, c, ld
+
+
+def conv2d_out_hw(h, w, k, padding):
+    """Height and width of a stride-1 convolution's output."""
+    return (h, w) if padding == "same" else (h - k + 1, w - k + 1)
+
+
+def window2d_out_hw(h, w, window, stride, padding):
+    """Height and width of a pooled map (TensorFlow's SAME / VALID arithmetic)."""
+    if padding == "same":
+        return -(-h // stride[0]), -(-w // stride[1])
+    return (h - window[0]) // stride[0] + 1, (w - window[1]) // stride[1] + 1
+
+
+def conv2d_workspace_floats(bsz, h, w, cin, k, cout, padding) -> int:
+    """Floats of the workspace ``conv2d_bwd`` needs for the filter and bias gradients of this shape."""
+    return int(_lib.load().nm_conv2d_workspace_bytes(bsz, h, w, cin, k, cout, PADDINGS[padding])) // 4
+
+
+def conv2d_fwd(x, filt, bias, y, padding, algo=0):
+    """y [B, OH, OW, Cout] = conv2d(x [B, H, W, Cin], filt [k, k, Cin, Cout]) + bias at stride 1 (nm_conv2d_fwd)."""
+    bsz, h, w, cin, ldx = _nhwc(x, "conv2d_fwd x")
+    _f32(filt), _f32(bias)
+    assert filt.dim() == 4 and filt.is_contiguous() and filt.shape[0] == filt.shape[1] and filt.shape[2] == cin, "filter"
+    k, cout = int(filt.shape[0]), int(filt.shape[3])
+    assert bias.is_contiguous() and bias.numel() == cout
+    oh, ow = conv2d_out_hw(h, w, k, padding)
+    assert tuple(y.shape) == (bsz, oh, ow, cout), (tuple(y.shape), (bsz, oh, ow, cout))
+    ldy = _nhwc(y, "conv2d_fwd y")[4]
+    _lib.check(_lib.load().nm_conv2d_fwd(_stream(), x.data_ptr(), ldx, bsz, h, w, cin, filt.data_ptr(), k, cout,
+                                         PADDINGS[padding], bias.data_ptr(), y.data_ptr(), ldy, int(algo)), "nm_conv2d_fwd")
+    return y
+
+
+def conv2d_bwd(x, filt, dy, padding, dx=None, accumulate_dx=False, dfilt=None, dbias=None, accumulate_params=True,
+               workspace=None, algo=0):
+    """The gradient of ``conv2d_fwd``: dx (+)= conv2d^T(dy, filt); dfilt / dbias (+)= the filter / bias gradients
+    (nm_conv2d_bwd; deterministic).  ``workspace``: conv2d_workspace_floats floats, needed with ``dfilt`` / ``dbias``."""
+    bsz, h, w, cin, ldx = _nhwc(x, "conv2d_bwd x")
+    _f32(filt)
+    assert filt.dim() == 4 and filt.is_contiguous() and filt.shape[0] == filt.shape[1] and filt.shape[2] == cin, "filter"
+    k, cout = int(filt.shape[0]), int(filt.shape[3])
+    oh, ow = conv2d_out_hw(h, w, k, padding)
+    assert tuple(dy.shape) == (bsz, oh, ow, cout)
+    lddy = _nhwc(dy, "conv2d_bwd dy")[4]
+    lddx = 0
+    if dx is not None:
+        assert tuple(dx.shape) == (bsz, h, w, cin)
+        lddx = _nhwc(dx, "conv2d_bwd dx")[4]
+    assert dfilt is None or (_f32(dfilt).is_contiguous() and dfilt.numel() == filt.numel())
+    assert dbias is None or (_f32(dbias).is_contiguous() and dbias.numel() == cout)
+    _lib.check(_lib.load().nm_conv2d_bwd(_stream(), x.data_ptr(), ldx, bsz, h, w, cin, filt.data_ptr(), k, cout,
+                                         PADDINGS[padding], dy.data_ptr(), lddy, _p(dx), lddx, int(bool(accumulate_dx)),
+                                         _p(dfilt), _p(dbias), int(bool(accumulate_params)), _p(workspace),
+                                         0 if workspace is None else workspace.numel() * 4, int(algo)), "nm_conv2d_bwd")
+
+
+def bn2d_fwd(x, gamma, beta, y, training, relu, moving_mean=None, moving_var=None, batch_mean=None, batch_var=None,
+             eps=BN_EPSILON, momentum=BN_MOMENTUM):
+    """Batch normalisation over the rows of x [rows, C] (+ ReLU) (nm_bn2d_fwd): training mode writes ``batch_mean`` /
+    ``batch_var`` and, when given, updates the moving statistics; inference reads the moving statistics."""
+    c = x.shape[1]
+    ldx, ldy = _ld2(x, c, "bn2d_fwd x"), _ld2(y, c, "bn2d_fwd y")
+    assert y.shape == x.shape
+    for t in (gamma, beta, moving_mean, moving_var, batch_mean, batch_var):
+        assert t is None or (_f32(t).is_contiguous() and t.numel() == c)
+    _lib.check(_lib.load().nm_bn2d_fwd(_stream(), x.data_ptr(), ldx, x.shape[0], c, gamma.data_ptr(), beta.data_ptr(),
+                                       float(eps), float(momentum), int(bool(training)), int(bool(relu)),
+                                       _p(moving_mean), _p(moving_var), _p(batch_mean), _p(batch_var), y.data_ptr(), ldy),
+               "nm_bn2d_fwd")
+    return y
+
+
+def bn2d_bwd(x, y, dy, gamma, batch_mean, batch_var, relu, sums, dx=None, accumulate_dx=False, dgamma=None, dbeta=None,
+             accumulate_params=True, eps=BN_EPSILON):
+    """The gradient of the training-mode ``bn2d_fwd`` (nm_bn2d_bwd); ``sums`` [2C] is scratch."""
+    c = x.shape[1]
+    ldx, lddy = _ld2(x, c, "bn2d_bwd x"), _ld2(dy, c, "bn2d_bwd dy")
+    ldy = 0 if y is None else _ld2(y, c, "bn2d_bwd y")
+    lddx = 0 if dx is None else _ld2(dx, c, "bn2d_bwd dx")
+    assert dy.shape == x.shape and (dx is None or dx.shape == x.shape) and (y is None or y.shape == x.shape)
+    assert _f32(sums).is_contiguous() and sums.numel() == 2 * c
+    for t in (gamma, batch_mean, batch_var, dgamma, dbeta):
+        assert t is None or (_f32(t).is_contiguous() and t.numel() == c)
+    _lib.check(_lib.load().nm_bn2d_bwd(_stream(), x.data_ptr(), ldx, _p(y), ldy, dy.data_ptr(), lddy, x.shape[0], c,
+                                       gamma.data_ptr(), batch_mean.data_ptr(), batch_var.data_ptr(), float(eps),
+                                       int(bool(relu)), _p(dx), lddx, int(bool(accumulate_dx)), _p(dgamma), _p(dbeta),
+                                       int(bool(accumulate_params)), sums.data_ptr()), "nm_bn2d_bwd")
+
+
+def window2d_fwd(mode, x, y, window, stride, padding="valid", argmax=None):
+    """y [B, OH, OW, C] = max / average of x [B, H, W, C] over ``window`` at ``stride`` (nm_window2d_fwd); ``argmax``
+    (int32, the shape of y, contiguous): where the first maximum lies, for ``window2d_bwd``."""
+    bsz, h, w, c, ldx = _nhwc(x, "window2d_fwd x")
+    oh, ow = window2d_out_hw(h, w, window, stride, padding)
+    assert tuple(y.shape) == (bsz, oh, ow, c), (tuple(y.shape), (bsz, oh, ow, c))
+    ldy = _nhwc(y, "window2d_fwd y")[4]
+    assert argmax is None or (_i32(argmax).is_contiguous() and argmax.numel() == y.numel())
+    _lib.check(_lib.load().nm_window2d_fwd(_stream(), x.data_ptr(), ldx, bsz, h, w, c, window[0], window[1], stride[0],
+                                           stride[1], PADDINGS[padding], WINDOW_MODES[mode], y.data_ptr(), ldy,
+                                           _p(argmax)), "nm_window2d_fwd")
+    return y
+
+
+def window2d_bwd(mode, dy, dx, window, stride, padding="valid", argmax=None, accumulate=False):
+    """dx [B, H, W, C] (+)= the gradient of ``window2d_fwd`` (nm_window2d_bwd); every element is written."""
+    bsz, h, w, c, lddx = _nhwc(dx, "window2d_bwd dx")
+    oh, ow = window2d_out_hw(h, w, window, stride, padding)
+    assert tuple(dy.shape) == (bsz, oh, ow, c)
+    lddy = _nhwc(dy, "window2d_bwd dy")[4]
+    assert argmax is None or (_i32(argmax).is_contiguous() and argmax.numel() == dy.numel())
+    _lib.check(_lib.load().nm_window2d_bwd(_stream(), dy.data_ptr(), lddy, _p(argmax), bsz, h, w, c, window[0], window[1],
+                                           stride[0], stride[1], PADDINGS[padding], WINDOW_MODES[mode], dx.data_ptr(),
+                                           lddx, int(bool(accumulate))), "nm_window2d_bwd")
+    return dx
+
+
+def map_columns(src, dst, inverse=False):
+    """dst [B, W, H*C] = the columns of the map src [B, H, W, C], left to right (nm_map_columns); ``inverse``: the map
+    dst [B, H, W, C] from its columns src [B, W, H*C]."""
+    bsz, h, w, c = (dst if inverse else src).shape
+    cols = src if inverse else dst
+    assert tuple(cols.shape) == (bsz, w, h * c) and _f32(src).is_contiguous() and _f32(dst).is_contiguous()
+    _lib.check(_lib.load().nm_map_columns(_stream(), src.data_ptr(), dst.data_ptr(), bsz, h, w, c, int(bool(inverse))),
+               "nm_map_columns")
+    return dst

@@ -169,9 +169,10 @@ class RunContext:
 
 def part_reads(part) -> List[Any]:
     """The model parts whose tensors ``part`` reads in its forward pass, and hands gradients to in its backward pass:
-    its input sequence, the object of a gradient-reversal view, the encoder it cross-attends to."""
+    its input sequence, the object of a gradient-reversal view, the encoder it cross-attends to, the CNN behind a view of
+    its maps' columns."""
     found = []
-    for attr in ("input_sequence", "_reversed_object", "input_for_cross_attention"):
+    for attr in ("input_sequence", "_reversed_object", "input_for_cross_attention", "_cnn"):
         other = getattr(part, attr, None)
         if other is not None and not any(other is f for f in found):
             found.append(other)

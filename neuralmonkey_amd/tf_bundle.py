@@ -319,6 +319,8 @@ def export_store(store, prefix: str, global_step: Optional[int] = None, with_ada
             tensors[name + s1] = np.zeros_like(arr)
         m, v = store.adam_m.cpu().numpy(), store.adam_v.cpu().numpy()
         for name, spec in store.specs.items():
+            if not spec.trainable:         # no optimizer makes slots for them (batch norm's moving statistics)
+                continue
             shape = tf_shape(name, spec.shape)
             tensors[name + s0] = m[spec.offset:spec.offset + spec.size].reshape(shape)
             tensors[name + s1] = v[spec.offset:spec.offset + spec.size].reshape(shape)
@@ -348,11 +350,12 @@ def import_store(store, prefix: str, strict: bool = True) -> Dict[str, object]:
         raise KeyError("variables missing from the checkpoint: {}".format(missing[:8]))
     store.load_state_dict(values, strict=False)
     from .variables import find_slot_suffixes
-    s0, s1 = store.slot_suffixes = find_slot_suffixes(bundle, values, store.slot_suffixes)
-    if all(n + s0 in bundle and n + s1 in bundle for n in values) and values:
+    slotted = [n for n in values if store.specs[n].trainable]        # non-trainable variables have no slots
+    s0, s1 = store.slot_suffixes = find_slot_suffixes(bundle, slotted, store.slot_suffixes)
+    if all(n + s0 in bundle and n + s1 in bundle for n in slotted) and slotted:
         import torch
         m, v = store.ensure_adam()
-        for name in values:
+        for name in slotted:
             spec = store.specs[name]
             m[spec.offset:spec.offset + spec.size] = torch.from_numpy(
                 np.asarray(bundle[name + s0], np.float32).reshape(-1)).to(m.device)

@@ -230,6 +230,8 @@ class VariableStore:
         if self.adam_m is not None:
             m, v = self.adam_m.cpu().numpy(), self.adam_v.cpu().numpy()
             for name, spec in self.specs.items():
+                if not spec.trainable:     # no optimizer makes slots for them (batch norm's moving statistics)
+                    continue
                 arrays[(name + self.slot_suffixes[0]).replace("/", "|")] = m[spec.offset:spec.offset + spec.size].reshape(spec.shape)
                 arrays[(name + self.slot_suffixes[1]).replace("/", "|")] = v[spec.offset:spec.offset + spec.size].reshape(spec.shape)
         if global_step is not None:
@@ -249,7 +251,7 @@ class VariableStore:
             values = {k.replace("|", "/"): data[k] for k in data.files}
         self.load_state_dict(values, strict)
         self.take_checkpoint_only(values)
-        names = [n for n in self.specs if n in values]
+        names = [n for n in self.specs if n in values and self.specs[n].trainable]
         s0, s1 = self.slot_suffixes = find_slot_suffixes(values, names, self.slot_suffixes)
         if names and all(n + s0 in values and n + s1 in values for n in names):
             m, v = self.ensure_adam()
