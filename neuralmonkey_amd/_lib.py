@@ -200,6 +200,13 @@ IMAGE_SIGNATURES = {
     "nm_map_columns": (I, [P, P, P, L, L, L, L, I]),
 }
 
+# ... and every symbol include/nmhip_reward.h declares (the rewards of SelfCriticalObjective, csrc/nm_reward.hip)
+REWARD_SIGNATURES = {
+    "nm_sentence_reward_max_tokens": (L, []),
+    "nm_sentence_reward": (I, [P, I, P, L, L, P, L, L, L, ctypes.c_int32, P]),
+    "nm_reinforce_weights": (I, [P, P, P, P, L, L, F, P, P, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -259,7 +266,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
                               + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
-                              + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())):
+                              + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
+                              + list(REWARD_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -340,6 +340,7 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
                                      [st.contexts.view(rows, -1) for st in att_states], out_all)
         logits = ctx.buffer(key + ("logits",), (rows, v))
         self.state_to_logits(ctx, out_all, logits)
+        self._keep_train_argmax(ctx, logits, steps, bsz)
         loss_rows = ctx.buffer(key + ("loss_rows",), (rows,))
         db_partial = None
         if want_grad and not self.tie_embeddings and ops.xent_colsum_ok(logits):

@@ -96,11 +96,14 @@ class GeneralDecoderMixin:
 
     # -- one step --------------------------------------------------------------------------------
     def general_step(self, tape: F.Tape, emb_in: F.Var, state: List[F.Var], sessions, w_outs, train: bool,
-                     t: int, project: bool = True, x_proj=None, out_views=None):
+                     t: int, project: bool = True, x_proj=None, out_views=None, site: Optional[str] = None):
         """Decoder.next_state (decoders/decoder.py:279-358).  ``state`` = [prev_rnn_state,
-        prev_rnn_output, *prev_contexts]; returns (output, new_state)."""
+        prev_rnn_output, *prev_contexts]; returns (output, new_state).  ``site``: a second loop over the same decoder
+        in one step (the taped runtime loop beside the teacher-forced one) names its dropout sites apart -- TensorFlow
+        instantiates the body once per while_loop, with masks of its own."""
         ctx = tape.ctx
         keep = self.dropout_keep_prob
+        name = self.name if site is None else "{}/{}".format(self.name, site)
         prev_state, prev_out, prev_ctxs = state[0], state[1], state[2:]
         if self._attention_on_input:                                   # :264-277
             w = tape.param(self, "attention_decoder/input_projection/kernel")
@@ -111,7 +114,7 @@ class GeneralDecoderMixin:
                 x = F.linear(tape, part, tape.rows(w, row, row + sz), b if x is None else None, out=x,
                              accumulate=x is not None)
                 row += sz
-            rnn_input = F.dropout(tape, x, keep, train, ctx.salt(self.name, "input_projection", t))
+            rnn_input = F.dropout(tape, x, keep, train, ctx.salt(name, "input_projection", t))
         else:
             rnn_input = emb_in
         if isinstance(self._cell_obj, LSTMCell):                       # :309-325
@@ -135,13 +138,13 @@ class GeneralDecoderMixin:
             if self._cond_cell is not None:
                 kw2 = {"out": s_view} if isinstance(self._cond_cell, NematusGRUCell) else {}
                 cell_output, (next_state,) = self._cond_cell.step(tape, F.concat(tape, contexts), (next_state,), **kw2)
-        contexts = [F.dropout(tape, c, keep, train, ctx.salt(self.name, "context", i, t))
+        contexts = [F.dropout(tape, c, keep, train, ctx.salt(name, "context", i, t))
                     for i, c in enumerate(contexts)]                   # :331-332
-        cell_output = F.dropout(tape, cell_output, keep, train, ctx.salt(self.name, "cell_output", t))
+        cell_output = F.dropout(tape, cell_output, keep, train, ctx.salt(name, "cell_output", t))
         if not project:      # the caller projects the outputs of all steps at once (nothing of it feeds the recurrence)
             return None, [next_state, cell_output] + contexts
         output = self.output_projection.apply_var(tape, self, cell_output, emb_in, contexts, train,
-                                                  ctx.salt(self.name, "output_projection", t))
+                                                  ctx.salt(name, "output_projection", t))
         return output, [next_state, cell_output] + contexts
 
     def _logit_params(self, tape: F.Tape):
@@ -213,6 +216,7 @@ class GeneralDecoderMixin:
                                                        ctx.salt(self.name, "output_projection", 0))
         w, trans_b, bias = self._logit_params(tape)
         logits = F.linear(tape, out_all, w, bias, trans_b=trans_b)
+        self._keep_train_argmax(ctx, logits.data, steps, bsz)
         loss_rows = F.xent(tape, logits, tgt.reshape(-1), self.xent_weights(tmask.reshape(-1)), grad_scale,
                            self.label_smoothing or 0.0)
         loss_sum = ctx.buffer((id(self), "gtrain", "loss_sum"), (1,))
@@ -224,6 +228,74 @@ class GeneralDecoderMixin:
                  "dlogits": logits.data if want_grad else None, "logits": logits.data,
                  "loss_rows": loss_rows, "loss_layout": "tb"}
         return TrainResult(loss_sum, self.train_token_count(ctx), steps, saved)
+
+    # -- self-critical training (trainers/self_critical_objective.py) ------------------------------------------
+    def _keep_train_argmax(self, ctx, logits: torch.Tensor, steps: int, bsz: int) -> None:
+        """tf.argmax(train_logits, axis=2) for an objective that asked for it (``want_train_argmax`` in ``ctx.memo``):
+        taken HERE, before the recording cross entropy turns the logits into their gradient.  Nobody asked: nothing
+        is launched."""
+        if not ctx.memo.get((id(self), "want_train_argmax")):
+            return
+        out = ctx.buffer((id(self), "train_argmax", steps, bsz), (steps, bsz), torch.int32)
+        ops.row_stats(logits, None, None, out.view(-1))
+        ctx.memo[(id(self), "train_argmax")] = out
+
+    def taped_runtime_loop(self, ctx, record: bool = True) -> dict:
+        """The greedy loop of ``Decoder._runtime_loop(keep_logits=True)`` on a recording tape, for every decoder
+        configuration: ``general_step`` with its projection, logits by ``F.linear``, the full-vocabulary argmax into
+        ``ops.greedy_update``, the next input ``F.embedding`` of the step's symbols, the stopping rule through
+        ``Session.decode_chunks``, the same mask.  Dropout follows the fed ``train_mode``; the sites inside the loop
+        body draw masks of their own (``site="runtime"``), the initial state and the attentions' states are the
+        tensors the teacher-forced loop reads.
+
+        Returns the tape and what ``_general_backward`` reads of a train result, ``logits`` [T', B, V] (a Var whose
+        gradient buffer is the logits themselves, as ``F.xent`` leaves it), ``argmax`` (the raw argmax of every step's
+        logits, ``<pad>`` rows of finished sentences included), ``symbols`` and ``mask`` [T', B] int32, ``steps`` (the
+        reference's loop length) and ``enqueued`` = T' >= steps (steps past the first all-finished one carry mask 0)."""
+        from ..vocabulary import END_TOKEN_INDEX, START_TOKEN_INDEX
+        from .decoder import CHECK_EVERY
+        train = bool(ctx.fed(self.train_mode))
+        key = (id(self), "grun")
+        tape = F.Tape(ctx, key, recording=record)
+        bsz = int(ctx.fed(self.batch_size))
+        tmax, v = self.max_output_len, len(self.vocabulary)
+        keep = self.dropout_keep_prob
+
+        table = tape.named_param(self.embedding_matrix_name)
+        enc_outs = [tape.leaf(enc.output(ctx), needs_grad=True) for enc in self.encoders]
+        s0 = self.encoder_projection.apply_var(tape, self, self.rnn_size, enc_outs, bsz, train)
+        s0 = F.dropout(tape, s0, keep, train, ctx.salt(self.name, "initial_state"))
+        sessions = [a.tape_session(tape, train) for a in self.attentions]
+        state = [s0, s0] + [tape.leaf(tape.buf((bsz, a.context_vector_size), zero=True)) for a in self.attentions]
+        w, trans_b, bias = self._logit_params(tape)
+        logits_buf = ctx.buffer(key + ("logits",), (tmax * bsz, v))
+        logits_all = F.Var(logits_buf, logits_buf if record else None, record)
+
+        argmax = ctx.buffer(key + ("argmax",), (tmax, bsz), torch.int32, zero=True)
+        symbols = ctx.buffer(key + ("sym",), (tmax, bsz), torch.int32, zero=True)
+        omask = ctx.buffer(key + ("mask",), (tmax, bsz), torch.int32, zero=True)
+        finished = ctx.buffer(key + ("fin",), (bsz,), torch.int32, zero=True)
+        allfin = ctx.buffer(key + ("allfin",), (tmax,), torch.int32)
+        ops.fill(allfin, 1)
+        go = ctx.buffer(key + ("go",), (bsz,), torch.int32)
+        ops.fill(go, START_TOKEN_INDEX)
+        loop = {"state": state}
+
+        def launch(t0, n):
+            for t in range(t0, t0 + n):
+                emb = F.embedding(tape, table, go if t == 0 else symbols[t - 1])
+                emb = F.dropout(tape, emb, keep, train, ctx.salt(self.name, "runtime", "embedded_input", t))
+                out_t, loop["state"] = self.general_step(tape, emb, loop["state"], sessions, [None] * len(sessions),
+                                                         train, t, site="runtime")
+                lg = F.linear(tape, out_t, w, bias, out=tape.rows(logits_all, t * bsz, (t + 1) * bsz), trans_b=trans_b)
+                ops.row_stats(lg.data, None, None, argmax[t])
+                ops.greedy_update(argmax[t], finished, symbols[t], omask[t], END_TOKEN_INDEX, allfin[t:t + 1])
+        # (the tape is recorded from Python: the host reads every chunk's own flags before it records the next)
+        steps, enqueued = ctx.session.decode_chunks(tmax, CHECK_EVERY, launch, allfin, run_ahead=False)
+        logits = F.Var(logits_buf[:enqueued * bsz], logits_buf[:enqueued * bsz] if record else None, record)
+        return {"tape": tape, "enc_outs": enc_outs, "sessions": sessions, "bsz": bsz, "steps": steps,
+                "enqueued": enqueued, "logits": logits, "argmax": argmax[:enqueued], "symbols": symbols[:enqueued],
+                "mask": omask[:enqueued]}
 
     def _general_backward(self, ctx, res) -> None:
         sv = res.saved

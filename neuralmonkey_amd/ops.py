@@ -2005,3 +2005,47 @@ def map_columns(src, dst, inverse=False):
     _lib.check(_lib.load().nm_map_columns(_stream(), src.data_ptr(), dst.data_ptr(), bsz, h, w, c, int(bool(inverse))),
                "nm_map_columns")
     return dst
+
+
+# ---- rewards of self-critical training (include/nmhip_reward.h, csrc/nm_reward.hip) ----------------------------------------
+REWARD_KINDS = {"bleu": 0, "gleu": 1}
+
+
+def sentence_reward_max_tokens() -> int:
+    return int(_lib.load().nm_sentence_reward_max_tokens())
+
+
+def sentence_reward(kind, references, hypotheses, end_id, out=None):
+    """Sentence-level BLEU (``kind`` "bleu") or GLEU ("gleu") on token indices, one float per sentence
+    (trainers/self_critical_objective.py:124-231): ``references`` [T_ref, B] and ``hypotheses`` [T_hyp, B] are int32,
+    time-major, with unit batch stride and any row stride."""
+    lib = _lib.load()
+    _i32(references), _i32(hypotheses)
+    assert references.dim() == 2 and hypotheses.dim() == 2 and references.shape[1] == hypotheses.shape[1]
+    bsz = references.shape[1]
+    strides = []
+    for t in (references, hypotheses):
+        assert bsz == 1 or t.stride(1) == 1, "unit batch stride"
+        strides.append(t.stride(0) if t.shape[0] > 1 else max(t.stride(0), bsz))
+    if out is None:
+        out = torch.empty(bsz, dtype=torch.float32, device=references.device)
+    assert _f32(out).numel() == bsz and out.is_contiguous()
+    _lib.check(lib.nm_sentence_reward(_stream(), REWARD_KINDS[kind], references.data_ptr(), strides[0],
+                                      references.shape[0], hypotheses.data_ptr(), strides[1], hypotheses.shape[0], bsz,
+                                      int(end_id), out.data_ptr()), "nm_sentence_reward")
+    return out
+
+
+def reinforce_weights(reward, baseline, mask, weight, weights, grad_scale, inv_count):
+    """``weights`` [T, B] = -(reward - baseline)[None, :] * mask, ``grad_scale`` [1] = weight / sum(mask) and
+    ``inv_count`` [1] = 1 / sum(mask) from the int32 runtime ``mask`` [T, B], all on the device
+    (trainers/self_critical_objective.py:75-85,113-120): the operands of ``xent`` over the runtime logits."""
+    lib = _lib.load()
+    assert _i32(mask).dim() == 2 and mask.is_contiguous()
+    steps, bsz = mask.shape
+    for t, n in ((reward, bsz), (baseline, bsz), (weights, steps * bsz), (grad_scale, 1), (inv_count, 1)):
+        assert _f32(t).numel() == n and t.is_contiguous()
+    _lib.check(lib.nm_reinforce_weights(_stream(), reward.data_ptr(), baseline.data_ptr(), mask.data_ptr(), steps, bsz,
+                                        float(weight), weights.data_ptr(), grad_scale.data_ptr(), inv_count.data_ptr()),
+               "nm_reinforce_weights")
+    return weights

@@ -100,6 +100,24 @@ class GenericTrainer(GraphExecutor, Feedable):
         return self._tables[key]
 
     # -- the training step --------------------------------------------------------------------
+    def split_objectives(self):
+        """([(index, objective, weight)] of the objectives whose loss is their decoder's teacher-forced cost,
+        [(objective, weight)] of the self-critical ones).  A cost and a self-critical objective may share a decoder
+        (tests/self-critical.ini, 0.5 each): the second reuses the first's teacher-forced pass.  Two of a kind may not."""
+        from .self_critical_objective import SelfCriticalObjective
+        plain, critics = [], []
+        for i, obj in enumerate(self.objectives):
+            weight = 1.0 if obj.weight is None else float(obj.weight)
+            critic = isinstance(obj, SelfCriticalObjective)
+            others = [o for o, _ in critics] if critic else [o for _, o, _ in plain]
+            if any(o.decoder is obj.decoder for o in others):
+                raise NotImplementedError("two objectives over the decoder '{}' in one trainer".format(obj.decoder.name))
+            if critic:
+                critics.append((obj, weight))
+            else:
+                plain.append((i, obj, weight))
+        return plain, critics
+
     def _objective_gradients(self, outer) -> None:
         """Forward + backward of every objective into the (zeroed) flat gradient buffer.
 
@@ -122,12 +140,15 @@ class GenericTrainer(GraphExecutor, Feedable):
         for part in self.feedables:          # host -> device copies of the fed batch, into persistent buffers
             part.stage_inputs(ctx)
         train = bool(ctx.fed(self.train_mode)) if ctx.is_fed(self.train_mode) else True
+        plain, critics = self.split_objectives()
+        if critics and dp is not None and dp.world_size > 1:
+            raise NotImplementedError("SelfCriticalObjective with {} data-parallel ranks: the loss divides by the local "
+                                      "runtime mask".format(dp.world_size))
+        for obj, _ in critics:
+            ctx.memo[(id(obj.decoder), "want_train_argmax")] = True       # the teacher-forced pass keeps its argmax
         decoders, scales, counts = [], [], []
-        for i, obj in enumerate(self.objectives):
+        for i, obj, weight in plain:
             dec = obj.decoder
-            if dec in decoders:
-                raise NotImplementedError("two objectives over the decoder '{}' in one trainer".format(dec.name))
-            weight = 1.0 if obj.weight is None else float(obj.weight)
             # loss = sum(xent) / sum(mask): with data parallelism the denominator is the
             # GLOBAL token count and gradients are summed over ranks
             count = dec.train_token_count(ctx)
@@ -140,19 +161,29 @@ class GenericTrainer(GraphExecutor, Feedable):
             scales.append(scale)
             counts.append(count)
 
+        terms = []
+
         def forward_backward():
             """Every objective's forward + backward; encoders shared by several decoders run their
             backward pass once, on the summed gradient (RunContext.defer_backward)."""
             ctx.memo["backward_deferred"] = True
             results = []
+            del terms[:]
             for dec, scale in zip(decoders, scales):
                 res = dec._train_loop(ctx, want_grad=True, grad_scale=scale)     # pylint: disable=protected-access
                 dec.backward(ctx, res)
                 results.append(res)
+            # ... then the self-critical terms: each reuses the teacher-forced pass above where there is one, and its
+            # tape ADDS to the flat gradient (the hand-scheduled backward above overwrites its slices)
+            if critics:
+                sess.join_side()             # (the leaf products of the backward above write those slices on side lanes)
+            for obj, weight in critics:
+                terms.append(obj.forward_backward(ctx, weight))
             ctx.flush_backward()
             ctx.memo["backward_deferred"] = False
             return results
-        if sess.use_step_graphs and all(getattr(d, "graph_safe_training", lambda t: False)(train) for d in decoders):
+        if (sess.use_step_graphs and not critics      # (a self-critical term's loop length is read by the host)
+                and all(getattr(d, "graph_safe_training", lambda t: False)(train) for d in decoders)):
             # Taped (general-path) models launch hundreds of small kernels per step from Python:
             # the whole forward + backward becomes one HIP graph per batch shape.
             shapes = tuple(sorted((ph.name, tuple(np.shape(val))) for ph, val in ctx.feed.items()
@@ -163,6 +194,8 @@ class GenericTrainer(GraphExecutor, Feedable):
             results = forward_backward()
         for dec, res in zip(decoders, results):
             outer.memo[dec.train_loop_result.key] = res
+        for (obj, _), term in zip(critics, terms):
+            outer.memo[obj.result.key] = term
         sess.join_side()
 
     def _apply_gradients(self, ctx) -> int:
