@@ -207,6 +207,14 @@ REWARD_SIGNATURES = {
     "nm_reinforce_weights": (I, [P, P, P, P, L, L, F, P, P, P]),
 }
 
+# ... and every symbol include/nmhip_rl.h declares (the rewards and sample weights of ReinforceObjective, csrc/nm_rl.hip)
+RL_SIGNATURES = {
+    "nm_eval_sentence_score_max_tokens": (L, []),
+    "nm_eval_sentence_score": (I, [P, I, I, P, L, L, P, L, L, L, ctypes.c_int32, ctypes.c_int32, P]),
+    "nm_reinforce_sample_weights_max_samples": (L, []),
+    "nm_reinforce_sample_weights": (I, [P, P, P, P, L, L, L, I, I, F, F, P, P, P, P, P, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -267,7 +275,7 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
                               + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
                               + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
-                              + list(REWARD_SIGNATURES.items())):
+                              + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -300,6 +300,6 @@ class AutoregressiveDecoder(ModelPart):
             raise ValueError("temperature must be positive, got {}".format(temperature))
         if train_mode and (sample or temperature != 1.0):
             # (autoregressive.py:466-473 lets `sample` override teacher forcing; the only caller in the reference,
-            # trainers/rl_trainer.py:122-125 -- out of scope, SURVEY 8 -- passes train_mode=False)
+            # trainers/rl_trainer.py:122-125, passes train_mode=False)
             raise NotImplementedError("sampling / temperature in a teacher-forced loop are not implemented "
                                       "(the reference's only caller samples with train_mode=False)")

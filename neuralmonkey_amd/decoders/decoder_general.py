@@ -240,7 +240,8 @@ class GeneralDecoderMixin:
         ops.row_stats(logits, None, None, out.view(-1))
         ctx.memo[(id(self), "train_argmax")] = out
 
-    def taped_runtime_loop(self, ctx, record: bool = True) -> dict:
+    def taped_runtime_loop(self, ctx, record: bool = True, sample: bool = False, temperature: float = 1.0,
+                           tag: Optional[str] = None, replay: Optional[torch.Tensor] = None) -> dict:
         """The greedy loop of ``Decoder._runtime_loop(keep_logits=True)`` on a recording tape, for every decoder
         configuration: ``general_step`` with its projection, logits by ``F.linear``, the full-vocabulary argmax into
         ``ops.greedy_update``, the next input ``F.embedding`` of the step's symbols, the stopping rule through
@@ -251,11 +252,23 @@ class GeneralDecoderMixin:
         Returns the tape and what ``_general_backward`` reads of a train result, ``logits`` [T', B, V] (a Var whose
         gradient buffer is the logits themselves, as ``F.xent`` leaves it), ``argmax`` (the raw argmax of every step's
         logits, ``<pad>`` rows of finished sentences included), ``symbols`` and ``mask`` [T', B] int32, ``steps`` (the
-        reference's loop length) and ``enqueued`` = T' >= steps (steps past the first all-finished one carry mask 0)."""
+        reference's loop length) and ``enqueued`` = T' >= steps (steps past the first all-finished one carry mask 0).
+
+        ``sample`` / ``temperature`` (trainers/rl_trainer.py:120-126, autoregressive.py:440-493): every step's logits
+        are divided by the temperature IN PLACE (what the tape's linear keeps for its backward pass is its operands, so
+        the gradient that arrives in the logits' buffer is the one with respect to the divided logits: the caller folds
+        1 / temperature into its scale) and the next symbol is drawn by ``ops.gumbel_argmax`` with the salts of
+        ``sampling_salts`` (returned as ``salts``), or taken from row t of ``replay`` [T_rec, B] int32 -- recorded draws,
+        a reproducibility hook; ``argmax`` then holds the draws.  ``tag`` names a loop apart from the others of the same
+        step -- buffers, tape and the dropout sites inside the body -- so that several sampled loops stay alive at
+        once.  Without these arguments the loop is the greedy one, launch for launch."""
         from ..vocabulary import END_TOKEN_INDEX, START_TOKEN_INDEX
         from .decoder import CHECK_EVERY
+        self.check_sampling_args(False, sample, temperature)
         train = bool(ctx.fed(self.train_mode))
-        key = (id(self), "grun")
+        key = (id(self), "grun") if tag is None else (id(self), "grun", tag)
+        site = "runtime" if tag is None else "runtime/{}".format(tag)
+        drawn = sample or replay is not None
         tape = F.Tape(ctx, key, recording=record)
         bsz = int(ctx.fed(self.batch_size))
         tmax, v = self.max_output_len, len(self.vocabulary)
@@ -280,22 +293,31 @@ class GeneralDecoderMixin:
         go = ctx.buffer(key + ("go",), (bsz,), torch.int32)
         ops.fill(go, START_TOKEN_INDEX)
         loop = {"state": state}
+        salts = self.sampling_salts(ctx, tmax) if sample and replay is None else None
 
         def launch(t0, n):
             for t in range(t0, t0 + n):
                 emb = F.embedding(tape, table, go if t == 0 else symbols[t - 1])
-                emb = F.dropout(tape, emb, keep, train, ctx.salt(self.name, "runtime", "embedded_input", t))
+                emb = F.dropout(tape, emb, keep, train, ctx.salt(self.name, site, "embedded_input", t))
                 out_t, loop["state"] = self.general_step(tape, emb, loop["state"], sessions, [None] * len(sessions),
-                                                         train, t, site="runtime")
+                                                         train, t, site=site)
                 lg = F.linear(tape, out_t, w, bias, out=tape.rows(logits_all, t * bsz, (t + 1) * bsz), trans_b=trans_b)
-                ops.row_stats(lg.data, None, None, argmax[t])
+                if temperature != 1.0:                       # logits /= temperature (autoregressive.py:493)
+                    ops.ew("scale", lg.data, None, lg.data, alpha=1.0 / temperature)
+                if replay is not None:                       # (behind the recorded loop: <pad>, as the buffer holds)
+                    if t < replay.shape[0]:
+                        ops.copy(argmax[t], replay[t])
+                elif sample:                                 # tf.multinomial(logits, 1) (:470-473)
+                    ops.gumbel_argmax(lg.data, salts[t], argmax[t])
+                else:
+                    ops.row_stats(lg.data, None, None, argmax[t])
                 ops.greedy_update(argmax[t], finished, symbols[t], omask[t], END_TOKEN_INDEX, allfin[t:t + 1])
         # (the tape is recorded from Python: the host reads every chunk's own flags before it records the next)
         steps, enqueued = ctx.session.decode_chunks(tmax, CHECK_EVERY, launch, allfin, run_ahead=False)
         logits = F.Var(logits_buf[:enqueued * bsz], logits_buf[:enqueued * bsz] if record else None, record)
         return {"tape": tape, "enc_outs": enc_outs, "sessions": sessions, "bsz": bsz, "steps": steps,
                 "enqueued": enqueued, "logits": logits, "argmax": argmax[:enqueued], "symbols": symbols[:enqueued],
-                "mask": omask[:enqueued]}
+                "mask": omask[:enqueued], **({"salts": salts} if drawn else {})}
 
     def _general_backward(self, ctx, res) -> None:
         sv = res.saved

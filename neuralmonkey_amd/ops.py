@@ -2049,3 +2049,56 @@ def reinforce_weights(reward, baseline, mask, weight, weights, grad_scale, inv_c
                                         float(weight), weights.data_ptr(), grad_scale.data_ptr(), inv_count.data_ptr()),
                "nm_reinforce_weights")
     return weights
+
+
+# ---- REINFORCE with sentence-level feedback (include/nmhip_rl.h, csrc/nm_rl.hip) --------------------------------------------
+def eval_sentence_score_max_tokens() -> int:
+    return int(_lib.load().nm_eval_sentence_score_max_tokens())
+
+
+def eval_sentence_score(kind, order, references, hypotheses, end_id, pad_id, out=None):
+    """The evaluators' sentence BLEU (``kind`` "bleu", times 100) or GLEU ("gleu") over the 1- to ``order``-grams as
+    trainers/rl_trainer.py:83-115 scores a sample, on token indices, one float per sentence: ``references`` [T_ref, B]
+    and ``hypotheses`` [T_hyp, B] are int32, time-major, with unit batch stride and any row stride, each cut at its
+    first ``end_id`` or ``pad_id``."""
+    lib = _lib.load()
+    _i32(references), _i32(hypotheses)
+    assert references.dim() == 2 and hypotheses.dim() == 2 and references.shape[1] == hypotheses.shape[1]
+    bsz = references.shape[1]
+    strides = []
+    for t in (references, hypotheses):
+        assert bsz == 1 or t.stride(1) == 1, "unit batch stride"
+        strides.append(t.stride(0) if t.shape[0] > 1 else max(t.stride(0), bsz))
+    if out is None:
+        out = torch.empty(bsz, dtype=torch.float32, device=references.device)
+    assert _f32(out).numel() == bsz and out.is_contiguous()
+    _lib.check(lib.nm_eval_sentence_score(_stream(), REWARD_KINDS[kind], int(order), references.data_ptr(), strides[0],
+                                          references.shape[0], hypotheses.data_ptr(), strides[1], hypotheses.shape[0],
+                                          bsz, int(end_id), int(pad_id), out.data_ptr()), "nm_eval_sentence_score")
+    return out
+
+
+def reinforce_sample_weights(rewards, sent_logprobs, steps, weights, grad_scale, loss, baseline, weight=1.0,
+                             subtract_baseline=False, normalize=False, alpha=1.0, reward_counter=None, reward_sum=None):
+    """trainers/rl_trainer.py:149-185 in one launch: from ``rewards`` and ``sent_logprobs`` [S, B], the host list
+    ``steps`` of the S loop lengths and the baseline's two device scalars (updated in place) to the row weights
+    ``weights`` [S, T, B] of ``xent`` over each sample's logits, ``grad_scale`` [1] = ``weight``, ``loss`` [1] and
+    ``baseline`` [1]."""
+    import ctypes
+    lib = _lib.load()
+    samples, tmax, bsz = weights.shape
+    assert weights.is_contiguous() and _f32(weights) is not None and len(steps) == samples
+    for t, n in ((rewards, samples * bsz), (sent_logprobs, samples * bsz), (grad_scale, 1), (loss, 1), (baseline, 1),
+                 (reward_counter, 1), (reward_sum, 1)):
+        assert t is None or (_f32(t).numel() == n and t.is_contiguous())
+    host_steps = (ctypes.c_int32 * samples)(*[int(n) for n in steps])
+    _lib.check(lib.nm_reinforce_sample_weights(_stream(), rewards.data_ptr(), _p(sent_logprobs), host_steps, samples,
+                                               tmax, bsz, int(bool(subtract_baseline)), int(bool(normalize)),
+                                               float(alpha), float(weight), _p(reward_counter), _p(reward_sum),
+                                               weights.data_ptr(), grad_scale.data_ptr(), _p(loss),
+                                               baseline.data_ptr()), "nm_reinforce_sample_weights")
+    return weights
+
+
+def reinforce_sample_weights_max_samples() -> int:
+    return int(_lib.load().nm_reinforce_sample_weights_max_samples())

@@ -102,13 +102,16 @@ class GenericTrainer(GraphExecutor, Feedable):
     # -- the training step --------------------------------------------------------------------
     def split_objectives(self):
         """([(index, objective, weight)] of the objectives whose loss is their decoder's teacher-forced cost,
-        [(objective, weight)] of the self-critical ones).  A cost and a self-critical objective may share a decoder
-        (tests/self-critical.ini, 0.5 each): the second reuses the first's teacher-forced pass.  Two of a kind may not."""
+        [(objective, weight)] of the ones that decode for themselves: self-critical and REINFORCE).  A cost objective
+        and one of the second list may share a decoder (tests/self-critical.ini, 0.5 each): the second reuses the
+        first's teacher-forced pass.  Two of a kind may not -- nor a cost objective and a ReinforceObjective with
+        ``ce_smoothing``, whose own teacher-forced pass would overwrite the first's gradient."""
+        from .rl_trainer import ReinforceObjective
         from .self_critical_objective import SelfCriticalObjective
         plain, critics = [], []
         for i, obj in enumerate(self.objectives):
             weight = 1.0 if obj.weight is None else float(obj.weight)
-            critic = isinstance(obj, SelfCriticalObjective)
+            critic = isinstance(obj, (SelfCriticalObjective, ReinforceObjective))
             others = [o for o, _ in critics] if critic else [o for _, o, _ in plain]
             if any(o.decoder is obj.decoder for o in others):
                 raise NotImplementedError("two objectives over the decoder '{}' in one trainer".format(obj.decoder.name))
@@ -116,6 +119,10 @@ class GenericTrainer(GraphExecutor, Feedable):
                 critics.append((obj, weight))
             else:
                 plain.append((i, obj, weight))
+        for obj, _ in critics:
+            if getattr(obj, "ce_smoothing", 0.0) > 0.0 and any(o.decoder is obj.decoder for _, o, _ in plain):
+                raise NotImplementedError("a cost objective beside a ReinforceObjective with ce_smoothing over the "
+                                          "decoder '{}' in one trainer".format(obj.decoder.name))
         return plain, critics
 
     def _objective_gradients(self, outer) -> None:
@@ -142,10 +149,11 @@ class GenericTrainer(GraphExecutor, Feedable):
         train = bool(ctx.fed(self.train_mode)) if ctx.is_fed(self.train_mode) else True
         plain, critics = self.split_objectives()
         if critics and dp is not None and dp.world_size > 1:
-            raise NotImplementedError("SelfCriticalObjective with {} data-parallel ranks: the loss divides by the local "
-                                      "runtime mask".format(dp.world_size))
+            raise NotImplementedError("{} with {} data-parallel ranks: the loss is normalised by what the local rank "
+                                      "decoded".format(type(critics[0][0]).__name__, dp.world_size))
         for obj, _ in critics:
-            ctx.memo[(id(obj.decoder), "want_train_argmax")] = True       # the teacher-forced pass keeps its argmax
+            if getattr(obj, "wants_train_argmax", True):
+                ctx.memo[(id(obj.decoder), "want_train_argmax")] = True   # the teacher-forced pass keeps its argmax
         decoders, scales, counts = [], [], []
         for i, obj, weight in plain:
             dec = obj.decoder
@@ -173,8 +181,8 @@ class GenericTrainer(GraphExecutor, Feedable):
                 res = dec._train_loop(ctx, want_grad=True, grad_scale=scale)     # pylint: disable=protected-access
                 dec.backward(ctx, res)
                 results.append(res)
-            # ... then the self-critical terms: each reuses the teacher-forced pass above where there is one, and its
-            # tape ADDS to the flat gradient (the hand-scheduled backward above overwrites its slices)
+            # ... then the self-critical and REINFORCE terms: each reuses the teacher-forced pass above where there is
+            # one, and its tapes ADD to the flat gradient (the hand-scheduled backward above overwrites its slices)
             if critics:
                 sess.join_side()             # (the leaf products of the backward above write those slices on side lanes)
             for obj, weight in critics:
@@ -182,7 +190,7 @@ class GenericTrainer(GraphExecutor, Feedable):
             ctx.flush_backward()
             ctx.memo["backward_deferred"] = False
             return results
-        if (sess.use_step_graphs and not critics      # (a self-critical term's loop length is read by the host)
+        if (sess.use_step_graphs and not critics      # (such a term's loop lengths are read by the host)
                 and all(getattr(d, "graph_safe_training", lambda t: False)(train) for d in decoders)):
             # Taped (general-path) models launch hundreds of small kernels per step from Python:
             # the whole forward + backward becomes one HIP graph per batch shape.
