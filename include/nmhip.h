@@ -179,6 +179,9 @@ int nm_gru_seq_fwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_
 int nm_gru_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t ru_step, int64_t c_step,
                    const float* wgh, int64_t ld_g, int64_t stride_g, const float* wch, int64_t ld_c,
                    int64_t stride_c, void* workspace, int64_t workspace_bytes, uint32_t* sticky_error);
+/* nm_gru_seq_fwd_ex / nm_gru_seq_bwd_ex -- these two loops with the passes their callers launched around them (zero
+ * fills, nm_copy_cols, nm_gru_seq_shift, nm_gru_rh_seq) done by the loop kernels -- are declared in nmhip_gru_seq.h; the
+ * two calls above are those with nothing switched on. */
 /* The same for NematusGRUCell (nn/ortho_gru_cell.py:73-105: the reset gate multiplies the state projection AFTER the
  * product, c = tanh(x_c + r * (h.U_c + b_cs))): both recurrent products read h only, so a step is ONE product, one
  * element-wise stage and one hand-off.  Shapes, workspace ownership, give-up behaviour and `sticky_error` as

@@ -215,6 +215,13 @@ RL_SIGNATURES = {
     "nm_reinforce_sample_weights": (I, [P, P, P, P, L, L, L, I, I, F, F, P, P, P, P, P, P]),
 }
 
+# ... and every symbol include/nmhip_gru_seq.h declares (the GRU cluster loops with their glue passes folded in:
+# nm_gru_seq_fwd / nm_gru_seq_bwd with an nm_gru_seq_io descriptor behind the epilogue, csrc/nm_gru_cluster.hip)
+GRU_SEQ_SIGNATURES = {
+    "nm_gru_seq_fwd_ex": (I, [P, P, P, ctypes.c_int32, L, L, L, L, P, L, L, P, L, L, P, L, P]),
+    "nm_gru_seq_bwd_ex": (I, [P, P, P, ctypes.c_int32, L, L, P, L, L, P, L, L, P, L, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -231,6 +238,15 @@ class GruEpilogue(ctypes.Structure):
                 ("c", P), ("h0", P), ("hseq", P), ("hs_dir", L), ("hs_row", L), ("hs_time", L),
                 ("dxp", P), ("dx_dir", L), ("dx_row", L), ("dx_time", L),
                 ("dgpre", P), ("dcpre", P)]
+
+
+class GruSeqIo(ctypes.Structure):
+    """``nm_gru_seq_io`` of include/nmhip_gru_seq.h."""
+    _fields_ = [("zero_padded", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("final_state", P), ("final_row", L), ("final_dir", L),
+                ("hprev_seq", P), ("rh_seq", P), ("seq_dir", L), ("seq_row", L), ("seq_time", L),
+                ("h0_out", P),
+                ("d_final", P), ("dfinal_row", L), ("dfinal_dir", L)]
 
 
 class StepProblem(ctypes.Structure):
@@ -275,7 +291,8 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(CTC_SIGNATURES.items())
                               + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
                               + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
-                              + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())):
+                              + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
+                              + list(GRU_SEQ_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

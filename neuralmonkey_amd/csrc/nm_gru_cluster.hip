@@ -68,7 +68,25 @@ struct GruClu {
     unsigned* sticky;            // the caller's error word: set (never cleared) when this launch gave up; may be null
     int force_fail;              // test hook (nm_gru_seq_force_give_up): this launch raises its error word at once
     long* dbg;                   // timing probe (NM_CLU_DEBUG builds only)
+    // what the callers otherwise launch around a loop (nm_gru_seq_fwd_ex / nm_gru_seq_bwd_ex; each off when null / 0)
+    int zero_padded;             // the owners of a row's columns write zeros to its positions >= length (out / dxp)
+    float* fin; long fin_row, fin_dir;         // forward: state after each row's last valid step -> fin[row][d*fin_dir + col]
+    float* hprev_seq; float* rh_seq;           // forward: h_{t-1} and r * h_{t-1} at the step's position, zeros when padded
+    long sq_dir, sq_row, sq_time;
+    float* h0_out;               // forward: a copy of the initial state [ndir][R][H] (null h_in: zeros)
+    const float* dfin; long dfin_row, dfin_dir;    // backward: initial dh[d][row][col] = dfin[row][d*dfin_dir + col]
+    int dh_from_dfin;            // backward: 1 = initial dh is dfin (null: zero), 0 = it is read from e.dh
 };
+
+// clears every field of the fused inputs / outputs: the loops of the other cell types and the plain entry points
+static void clu_no_io(GruClu& q) {
+    q.zero_padded = 0;
+    q.fin = nullptr; q.fin_row = q.fin_dir = 0;
+    q.hprev_seq = q.rh_seq = nullptr; q.sq_dir = q.sq_row = q.sq_time = 0;
+    q.h0_out = nullptr;
+    q.dfin = nullptr; q.dfin_row = q.dfin_dir = 0;
+    q.dh_from_dfin = 0;
+}
 
 // ---- roles -------------------------------------------------------------------------------------------------------
 struct CluRole {
@@ -321,10 +339,11 @@ __global__ __launch_bounds__(512, 3) void gru_cluster_fwd_kernel(GruClu q) {
     const bool mine = epi && row < R;
     const long ro = (long)d * R + min(row, R - 1);
     const int len = (mine && q.e.lengths) ? q.e.lengths[row] : 0x7fffffff;
-    float hreg = mine ? q.e.h_in[ro * H + col] : 0.0f;
+    float hreg = (mine && q.e.h_in) ? q.e.h_in[ro * H + col] : 0.0f;          // (no h_in: h_0 = 0)
     const bool rev = ((q.e.rev_mask >> d) & 1) && q.e.lengths;
     u64* XA = q.xa + (long)role.cl * 16 * RT * H;        // this cluster's granules of r*h ...
     u64* XB = q.xb + (long)role.cl * 16 * RT * H;        // ... and of h'
+    if (mine && q.h0_out) q.h0_out[ro * H + col] = hreg;
 
     for (int t = 0; t < q.steps; ++t) {
         CLU_STAMP(0);
@@ -346,8 +365,14 @@ __global__ __launch_bounds__(512, 3) void gru_cluster_fwd_kernel(GruClu q) {
         CLU_STAMP(1);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            if (t == 0) clu_load_plain(q.e.h_in + (long)d * R * H, H, R, row0 + 16 * rt, k_wave, lane, a);
-            else clu_gather<RT, NCH>(XB, wave, lane, rt, 0, (unsigned)(2 * t), err, cw, a);
+            if (t > 0) clu_gather<RT, NCH>(XB, wave, lane, rt, 0, (unsigned)(2 * t), err, cw, a);
+            else if (q.e.h_in) clu_load_plain(q.e.h_in + (long)d * R * H, H, R, row0 + 16 * rt, k_wave, lane, a);
+            else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) a[c][j] = 0.0f;
+            }
             f32x4 ar = zero, au = zero;
             clu_mma(ar, a, wr);
             clu_mma(au, a, wu);
@@ -370,6 +395,11 @@ __global__ __launch_bounds__(512, 3) void gru_cluster_fwd_kernel(GruClu q) {
                 ru[col] = r;
                 ru[H + col] = u;
                 if (q.e.rh) q.e.rh[(long)t * q.rh_step + ro * H + col] = rh;
+                if (live && q.hprev_seq) {               // the operands of the recurrent kernels' gradients, by position
+                    const long o = d * q.sq_dir + (long)row * q.sq_row + (long)pos * q.sq_time + col;
+                    q.hprev_seq[o] = hreg;
+                    q.rh_seq[o] = rh;
+                }
             }
         }
         // ---- stage B: candidate + blend
@@ -402,6 +432,25 @@ __global__ __launch_bounds__(512, 3) void gru_cluster_fwd_kernel(GruClu q) {
             }
         }
         CLU_STAMP(7);
+    }
+    // behind the last hand-off (nobody waits for these stores): the final state where the caller reads it, and zeros
+    // at the positions past the row's length
+    if (mine) {
+        // (row and column through an empty asm: addresses formed from them cannot be hoisted into the loop above, where
+        // they would cost registers for all steps)
+        int trow = row, tcol = col;
+        asm volatile("" : "+v"(trow), "+v"(tcol));
+        if (q.fin) q.fin[(long)trow * q.fin_row + d * q.fin_dir + tcol] = hreg;
+        if (q.e.lengths) {
+            for (int p = max(len, 0); p < q.steps; ++p) {
+                if (q.zero_padded && q.e.out) q.e.out[d * q.e.o_dir + (long)trow * q.e.o_row + (long)p * q.e.o_time + tcol] = 0.0f;
+                if (q.hprev_seq) {
+                    const long o = d * q.sq_dir + (long)trow * q.sq_row + (long)p * q.sq_time + tcol;
+                    q.hprev_seq[o] = 0.0f;
+                    q.rh_seq[o] = 0.0f;
+                }
+            }
+        }
     }
     if (tid == 0 && q.sticky && __hip_atomic_load(err, NM_RLX_AGENT) != 0) __hip_atomic_store((gu32*)q.sticky, 1u, NM_RLX_AGENT);
 }
@@ -462,7 +511,11 @@ __global__ __launch_bounds__(512, 3) void gru_cluster_bwd_kernel(GruClu q) {
     const bool mine = epi && row < R;
     const long ro = (long)d * R + min(row, R - 1);
     const int len = (mine && q.e.lengths) ? q.e.lengths[row] : 0x7fffffff;
-    float dh = mine ? q.e.dh[ro * H + col] : 0.0f;
+    float dh = 0.0f;                                                    // dL/dh after the last step
+    if (mine) {
+        if (!q.dh_from_dfin) dh = q.e.dh[ro * H + col];
+        else if (q.dfin) dh = q.dfin[(long)row * q.dfin_row + d * q.dfin_dir + col];
+    }
     const bool rev = ((q.e.rev_mask >> d) & 1) && q.e.lengths;
     u64* XA = q.xa + (long)role.cl * 16 * RT * H;                       // dc_pre
     u64* XB = q.xb + (long)role.cl * 16 * RT * 2 * H;                   // [dr_pre | du_pre], two copies
@@ -549,7 +602,19 @@ __global__ __launch_bounds__(512, 3) void gru_cluster_bwd_kernel(GruClu q) {
         __syncthreads();
         if (epi) sB = clu_get(redB, RT, NW, ert, reg, ln);
     }
-    if (mine) q.e.dh[ro * H + col] = sB + dh;
+    if (mine) {
+        q.e.dh[ro * H + col] = sB + dh;
+        if (q.zero_padded && q.e.lengths) {              // (behind the last hand-off: nobody waits for these stores)
+            int trow = row, tcol = col;                  // (through an empty asm: nothing of this is hoisted into the loop)
+            asm volatile("" : "+v"(trow), "+v"(tcol));
+            for (int p = max(len, 0); p < q.steps; ++p) {
+                float* dx = q.e.dxp + d * q.e.dx_dir + (long)trow * q.e.dx_row + (long)p * q.e.dx_time;
+                dx[tcol] = 0.0f;
+                dx[H + tcol] = 0.0f;
+                dx[2 * H + tcol] = 0.0f;
+            }
+        }
+    }
     if (tid == 0 && q.sticky && __hip_atomic_load(err, NM_RLX_AGENT) != 0) __hip_atomic_store((gu32*)q.sticky, 1u, NM_RLX_AGENT);
 }
 
@@ -1302,6 +1367,7 @@ static void clu_fill(GruClu& q, const nm_gru_epilogue* e) {
     d.dxp = e->dxp; d.dx_dir = e->dx_dir; d.dx_row = e->dx_row; d.dx_time = e->dx_time;
     d.dgpre = e->dgpre; d.dcpre = e->dcpre;
     q.ndir = e->ndir;
+    clu_no_io(q);
     {   // test hook: the placement-independent path (what runs when an XCD does not get its tickets)
         const char* place = getenv("NM_CLUSTER_PLACEMENT");
         q.force_global = (place && strcmp(place, "blockidx") == 0) ? 1 : 0;
@@ -1318,22 +1384,52 @@ static void clu_fill(GruClu& q, const nm_gru_epilogue* e) {
 #endif
 }
 
-extern "C" int nm_gru_seq_fwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t h_step,
-                              int64_t ru_step, int64_t rh_step, int64_t c_step, const float* wgh, int64_t ld_g,
-                              int64_t stride_g, const float* wch, int64_t ld_c, int64_t stride_c,
-                              void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
-    NM_REQUIRE(e && wgh && wch && workspace, "nm_gru_seq_fwd: null pointer / workspace");
+// mirrors include/nmhip_gru_seq.h: what the callers of the plain entry points launch around a loop, done by the loop
+struct nm_gru_seq_io {
+    int32_t zero_padded, reserved;
+    float* final_state; int64_t final_row, final_dir;
+    float* hprev_seq; float* rh_seq; int64_t seq_dir, seq_row, seq_time;
+    float* h0_out;
+    const float* d_final; int64_t dfinal_row, dfinal_dir;
+};
+
+// io == null: the plain entry point (h_in required, nothing fused)
+static int gru_seq_fwd_launch(const char* who, void* stream, const nm_gru_epilogue* e, const nm_gru_seq_io* io,
+                              int32_t steps, int64_t h_step, int64_t ru_step, int64_t rh_step, int64_t c_step,
+                              const float* wgh, int64_t ld_g, int64_t stride_g, const float* wch, int64_t ld_c,
+                              int64_t stride_c, void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
+    NM_REQUIRE(e && wgh && wch && workspace, "%s: null pointer / workspace", who);
     NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2,
-               "nm_gru_seq_fwd: bad shape R=%ld H=%ld", (long)e->R, (long)e->H);
-    NM_REQUIRE(e->xp && e->h_in && e->h_out && e->ru, "nm_gru_seq_fwd: missing operand");
-    NM_REQUIRE(nm_aligned16(e->h_in) && nm_aligned16(workspace), "nm_gru_seq_fwd: operands must be 16-byte aligned");
+               "%s: bad shape R=%ld H=%ld", who, (long)e->R, (long)e->H);
+    NM_REQUIRE(e->xp && (e->h_in || io) && e->h_out && e->ru, "%s: missing operand", who);
+    NM_REQUIRE(nm_aligned16(e->h_in) && nm_aligned16(workspace), "%s: operands must be 16-byte aligned", who);
+    if (io) {
+        const int64_t H = e->H;
+        const bool two = e->ndir == 2;
+        NM_REQUIRE(!io->final_state || (io->final_row >= H && io->final_dir >= 0 && (!two || io->final_dir >= H)),
+                   "%s: inconsistent strides of final_state (row %ld, direction %ld, H %ld)", who, (long)io->final_row,
+                   (long)io->final_dir, (long)H);
+        NM_REQUIRE((io->hprev_seq != nullptr) == (io->rh_seq != nullptr), "%s: hprev_seq and rh_seq come together", who);
+        NM_REQUIRE(!io->hprev_seq || (io->seq_row >= H && io->seq_time >= H && io->seq_dir >= 0 && (!two || io->seq_dir >= H)),
+                   "%s: inconsistent strides of hprev_seq / rh_seq (direction %ld, row %ld, time %ld, H %ld)", who,
+                   (long)io->seq_dir, (long)io->seq_row, (long)io->seq_time, (long)H);
+        NM_REQUIRE(!io->zero_padded || e->out, "%s: zero_padded without out", who);
+        NM_REQUIRE(!io->h0_out || (io->h0_out != e->h_in && io->h0_out != e->h_out), "%s: h0_out may not alias h_in / h_out", who);
+    }
     CluShape s;
-    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "nm_gru_seq_fwd: shape R=%ld H=%ld ndir=%d not supported "
-               "(nm_gru_seq_supported)", (long)e->R, (long)e->H, (int)e->ndir);
-    NM_REQUIRE(workspace_bytes >= nm_gru_seq_workspace_bytes(e->R, e->H, e->ndir), "nm_gru_seq_fwd: workspace too small");
+    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported "
+               "(nm_gru_seq_supported)", who, (long)e->R, (long)e->H, (int)e->ndir);
+    NM_REQUIRE(workspace_bytes >= nm_gru_seq_workspace_bytes(e->R, e->H, e->ndir), "%s: workspace too small", who);
     if (steps == 0) return NM_OK;
     GruClu q;
     clu_fill(q, e);
+    if (io) {
+        q.zero_padded = io->zero_padded ? 1 : 0;
+        q.fin = io->final_state; q.fin_row = io->final_row; q.fin_dir = io->final_dir;
+        q.hprev_seq = io->hprev_seq; q.rh_seq = io->rh_seq;
+        q.sq_dir = io->seq_dir; q.sq_row = io->seq_row; q.sq_time = io->seq_time;
+        q.h0_out = io->h0_out;
+    }
     q.steps = steps; q.nrb = s.nrb;
     q.h_step = h_step; q.ru_step = ru_step; q.rh_step = rh_step; q.c_step = c_step;
     q.wg = wgh; q.ldg = ld_g; q.sg = stride_g; q.wc = wch; q.ldc = ld_c; q.sc = stride_c;
@@ -1343,7 +1439,7 @@ extern "C" int nm_gru_seq_fwd(void* stream, const nm_gru_epilogue* e, int32_t st
     q.xb = q.xa + s.granules;
     hipStream_t st = nm_stream(stream);
     if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * 2, st) != hipSuccess)
-        NM_FAIL(NM_ERR_HIP, "nm_gru_seq_fwd: memset failed");
+        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
     const size_t lds = (size_t)s.NW * s.RT * 3 * 1024;
     bool ok;
     if (s.RT == 1) {
@@ -1353,30 +1449,63 @@ extern "C" int nm_gru_seq_fwd(void* stream, const nm_gru_epilogue* e, int32_t st
         ok = clu_prepare(gru_cluster_fwd_kernel<2>, lds);
         if (ok) hipLaunchKernelGGL((gru_cluster_fwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, q);
     }
-    if (!ok) NM_FAIL(NM_ERR_HIP, "nm_gru_seq_fwd: the kernel cannot be made resident on this device");
-    NM_LAUNCH_CHECK("nm_gru_seq_fwd");
+    if (!ok) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
+    NM_LAUNCH_CHECK(who);
+}
+
+extern "C" int nm_gru_seq_fwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t h_step,
+                              int64_t ru_step, int64_t rh_step, int64_t c_step, const float* wgh, int64_t ld_g,
+                              int64_t stride_g, const float* wch, int64_t ld_c, int64_t stride_c,
+                              void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
+    return gru_seq_fwd_launch("nm_gru_seq_fwd", stream, e, nullptr, steps, h_step, ru_step, rh_step, c_step, wgh, ld_g,
+                              stride_g, wch, ld_c, stride_c, workspace, workspace_bytes, sticky_error);
+}
+
+// nm_gru_seq_fwd with the passes its callers launched around it done by the loop (``io``, every member optional):
+// e->h_in may be null (h_0 = 0); zeros at the padded positions of ``out``; the final state, h_{t-1} and r * h_{t-1} of
+// every position and a copy of h_0 where the caller reads them.
+extern "C" int nm_gru_seq_fwd_ex(void* stream, const nm_gru_epilogue* e, const nm_gru_seq_io* io, int32_t steps,
+                                 int64_t h_step, int64_t ru_step, int64_t rh_step, int64_t c_step, const float* wgh,
+                                 int64_t ld_g, int64_t stride_g, const float* wch, int64_t ld_c, int64_t stride_c,
+                                 void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
+    NM_REQUIRE(io, "nm_gru_seq_fwd_ex: null io (nm_gru_seq_fwd is the call without one)");
+    NM_REQUIRE(steps >= 1, "nm_gru_seq_fwd_ex: at least one step (the loop writes the fused outputs)");
+    return gru_seq_fwd_launch("nm_gru_seq_fwd_ex", stream, e, io, steps, h_step, ru_step, rh_step, c_step, wgh, ld_g,
+                              stride_g, wch, ld_c, stride_c, workspace, workspace_bytes, sticky_error);
 }
 
 // The whole BPTT loop: e->dh holds dL/dh after the last step on entry and dL/dh_0 on exit; step t reads ru + t*ru_step,
 // c + t*c_step, h_prev through hseq / h0, dout at the step's position, and writes the three pre-activation gradients
 // of the step's position into dxp.
-extern "C" int nm_gru_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t ru_step, int64_t c_step,
-                              const float* wgh, int64_t ld_g, int64_t stride_g, const float* wch, int64_t ld_c,
-                              int64_t stride_c, void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
-    NM_REQUIRE(e && wgh && wch && workspace, "nm_gru_seq_bwd: null pointer / workspace");
+static int gru_seq_bwd_launch(const char* who, void* stream, const nm_gru_epilogue* e, const nm_gru_seq_io* io,
+                              int32_t steps, int64_t ru_step, int64_t c_step, const float* wgh, int64_t ld_g,
+                              int64_t stride_g, const float* wch, int64_t ld_c, int64_t stride_c, void* workspace,
+                              int64_t workspace_bytes, uint32_t* sticky_error) {
+    NM_REQUIRE(e && wgh && wch && workspace, "%s: null pointer / workspace", who);
     NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2,
-               "nm_gru_seq_bwd: bad shape R=%ld H=%ld", (long)e->R, (long)e->H);
-    NM_REQUIRE(e->dh && e->ru && e->c && e->hseq && e->dxp, "nm_gru_seq_bwd: missing operand");
+               "%s: bad shape R=%ld H=%ld", who, (long)e->R, (long)e->H);
+    NM_REQUIRE(e->dh && e->ru && e->c && e->hseq && e->dxp, "%s: missing operand", who);
     NM_REQUIRE(nm_aligned16(wgh) && nm_aligned16(wch) && ld_g % 4 == 0 && ld_c % 4 == 0 && stride_g % 4 == 0 &&
                    stride_c % 4 == 0 && nm_aligned16(workspace),
-               "nm_gru_seq_bwd: kernels must be 16-byte aligned with leading dimensions %% 4 == 0");
+               "%s: kernels must be 16-byte aligned with leading dimensions %% 4 == 0", who);
+    if (io) {
+        const bool two = e->ndir == 2;
+        NM_REQUIRE(!io->d_final || (io->dfinal_row >= e->H && io->dfinal_dir >= 0 && (!two || io->dfinal_dir >= e->H)),
+                   "%s: inconsistent strides of d_final (row %ld, direction %ld, H %ld)", who, (long)io->dfinal_row,
+                   (long)io->dfinal_dir, (long)e->H);
+    }
     CluShape s;
-    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "nm_gru_seq_bwd: shape R=%ld H=%ld ndir=%d not supported "
-               "(nm_gru_seq_supported)", (long)e->R, (long)e->H, (int)e->ndir);
-    NM_REQUIRE(workspace_bytes >= nm_gru_seq_workspace_bytes(e->R, e->H, e->ndir), "nm_gru_seq_bwd: workspace too small");
+    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported "
+               "(nm_gru_seq_supported)", who, (long)e->R, (long)e->H, (int)e->ndir);
+    NM_REQUIRE(workspace_bytes >= nm_gru_seq_workspace_bytes(e->R, e->H, e->ndir), "%s: workspace too small", who);
     if (steps == 0) return NM_OK;
     GruClu q;
     clu_fill(q, e);
+    if (io) {
+        q.zero_padded = io->zero_padded ? 1 : 0;
+        q.dfin = io->d_final; q.dfin_row = io->dfinal_row; q.dfin_dir = io->dfinal_dir;
+        q.dh_from_dfin = 1;
+    }
     q.steps = steps; q.nrb = s.nrb;
     q.h_step = 0; q.ru_step = ru_step; q.rh_step = 0; q.c_step = c_step;
     q.wg = wgh; q.ldg = ld_g; q.sg = stride_g; q.wc = wch; q.ldc = ld_c; q.sc = stride_c;
@@ -1386,7 +1515,7 @@ extern "C" int nm_gru_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_t st
     q.xb = q.xa + s.granules;
     hipStream_t st = nm_stream(stream);
     if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * 5, st) != hipSuccess)
-        NM_FAIL(NM_ERR_HIP, "nm_gru_seq_bwd: memset failed");
+        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
     const size_t lds = (size_t)s.NW * s.RT * 2 * 1024;
     bool ok;
     if (s.RT == 1) {
@@ -1396,8 +1525,27 @@ extern "C" int nm_gru_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_t st
         ok = clu_prepare(gru_cluster_bwd_kernel<2>, lds);
         if (ok) hipLaunchKernelGGL((gru_cluster_bwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, q);
     }
-    if (!ok) NM_FAIL(NM_ERR_HIP, "nm_gru_seq_bwd: the kernel cannot be made resident on this device");
-    NM_LAUNCH_CHECK("nm_gru_seq_bwd");
+    if (!ok) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
+    NM_LAUNCH_CHECK(who);
+}
+
+extern "C" int nm_gru_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t ru_step, int64_t c_step,
+                              const float* wgh, int64_t ld_g, int64_t stride_g, const float* wch, int64_t ld_c,
+                              int64_t stride_c, void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
+    return gru_seq_bwd_launch("nm_gru_seq_bwd", stream, e, nullptr, steps, ru_step, c_step, wgh, ld_g, stride_g, wch, ld_c,
+                              stride_c, workspace, workspace_bytes, sticky_error);
+}
+
+// nm_gru_seq_bwd with the passes around it done by the loop: dL/dh after the last step is io->d_final in the caller's
+// layout (null: zero) -- e->dh is written only -- and with io->zero_padded the padded positions of dxp receive zeros.
+extern "C" int nm_gru_seq_bwd_ex(void* stream, const nm_gru_epilogue* e, const nm_gru_seq_io* io, int32_t steps,
+                                 int64_t ru_step, int64_t c_step, const float* wgh, int64_t ld_g, int64_t stride_g,
+                                 const float* wch, int64_t ld_c, int64_t stride_c, void* workspace,
+                                 int64_t workspace_bytes, uint32_t* sticky_error) {
+    NM_REQUIRE(io, "nm_gru_seq_bwd_ex: null io (nm_gru_seq_bwd is the call without one)");
+    NM_REQUIRE(steps >= 1, "nm_gru_seq_bwd_ex: at least one step (the loop writes the fused outputs)");
+    return gru_seq_bwd_launch("nm_gru_seq_bwd_ex", stream, e, io, steps, ru_step, c_step, wgh, ld_g, stride_g, wch, ld_c,
+                              stride_c, workspace, workspace_bytes, sticky_error);
 }
 
 // 1 when a cluster loop that used ``workspace`` gave up waiting (its results are garbage); reads 4 bytes back, so

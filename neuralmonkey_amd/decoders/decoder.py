@@ -302,7 +302,6 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
                 for att in self.attentions:
                     att.hidden_features(ctx)
         s_ext = ctx.buffer(key + ("s_ext",), (steps + 1, bsz, h))      # [s0 ; s_1 .. s_T]
-        ops.copy(s_ext[0], s0)
         s_all = s_ext[1:]
         ru_all = ctx.buffer(key + ("ru_all",), (steps, bsz, 2 * h))
         c_all = ctx.buffer(key + ("c_all",), (steps, bsz, h))
@@ -322,11 +321,18 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
                 self._recurrent(ctx, cell, xp, t, bsz * 3 * h, s_ext[t], s_all[t], ru_all[t], c_all[t], bufs,
                                 rh=rh_all[t], wt=wt)
         loop_h = gru.seq_mode(ctx.session, bsz, h, 1, cell["wg_h"], cell["wc_h"])
-        if loop_h:
-            # the whole recurrence as ONE launch (csrc/nm_gru_cluster.hip; padded when the kernels do not take h)
+        if loop_h == h and s0.is_contiguous() and s0.data_ptr() % 16 == 0:
+            # the whole recurrence as ONE launch (csrc/nm_gru_cluster.hip), which also puts s0 in front of its states
+            gru.seq_fwd(ctx, id(self), loop_h, steps, 1, bsz, h, xp, (0, 3 * h, bsz * 3 * h), s0, s_ext[1], bsz * h,
+                        ru_all[0], bsz * 2 * h, rh_all[0], bsz * h, c_all[0], bsz * h, cell["wg_h"], cell["wc_h"],
+                        h0_out=s_ext[0])
+        elif loop_h:
+            # ... at a padded hidden size (nn/gru.py)
+            ops.copy(s_ext[0], s0)
             gru.seq_fwd(ctx, id(self), loop_h, steps, 1, bsz, h, xp, (0, 3 * h, bsz * 3 * h), s_ext[0], s_ext[1], bsz * h,
                         ru_all[0], bsz * 2 * h, rh_all[0], bsz * h, c_all[0], bsz * h, cell["wg_h"], cell["wc_h"])
         else:
+            ops.copy(s_ext[0], s0)
             ctx.session.graphed((id(self), "train_loop", bsz, steps), time_loop)
         if overlap:
             ctx.session.join_side(0)
@@ -457,7 +463,8 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
                 vocabulary_projection_gradient()
 
         # ---- BPTT through the GRU (the only recurrence)
-        dh = ctx.buffer(key + ("dh",), (1, bsz, h), zero=True)
+        loop_h = gru.seq_mode(ctx.session, bsz, h, 1, cell["wg_h"], cell["wc_h"])
+        dh = ctx.buffer(key + ("dh",), (1, bsz, h), zero=loop_h != h)      # (the cluster loop starts from zero itself)
         dxp = ctx.buffer(key + ("dxp",), (rows, 3 * h))
         dgpre = ctx.buffer(key + ("dgpre",), (2, 1, bsz, 2 * h))
         dcpre = ctx.buffer(key + ("dcpre",), (1, bsz, h))
@@ -470,12 +477,11 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
             gru.bptt(steps, dh, d_s, seq_strides, sv["ru_all"], sv["c_all"], sv["s0"], s_all, seq_strides, dxp,
                      dxp_strides, cell["wg_h"].unsqueeze(0), cell["wc_h"].unsqueeze(0), None, 1, bsz, h, False,
                      dgpre, dcpre, drh)
-        loop_h = gru.seq_mode(ctx.session, bsz, h, 1, cell["wg_h"], cell["wc_h"])
         if loop_h:
-            ops.zero(dh)
+            fused = {"fused_io": True, "d_final": None} if loop_h == h else {}
             gru.seq_bwd(ctx, id(self), loop_h, steps, 1, bsz, h, dh, d_s, seq_strides, sv["ru_all"][0], bsz * 2 * h,
                         sv["c_all"][0], bsz * h, sv["s0"], s_all, seq_strides, dxp, dxp_strides, cell["wg_h"],
-                        cell["wc_h"])
+                        cell["wc_h"], **fused)
             if dp is not None:
                 dp.after_time_loops()
         else:

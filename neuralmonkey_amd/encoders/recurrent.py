@@ -183,8 +183,9 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
         wch = dir_batch("off_c", h)
 
         train = ctx.wants_backward(bool(ctx.fed(self.train_mode)))
-        states_raw = ctx.buffer((key, "states_raw"), (bsz, slen, c_out), zero=True)
-        hcur = ctx.buffer((key, "hcur"), (ndir, bsz, h), zero=True)
+        # (the per-step loop zeroes both inside its graph, the cluster loops write every element themselves)
+        states_raw = ctx.buffer((key, "states_raw"), (bsz, slen, c_out))
+        hcur = ctx.buffer((key, "hcur"), (ndir, bsz, h))
         hg = ctx.buffer((key, "hg"), (ndir, bsz, 2 * h))
         hc = ctx.buffer((key, "hc"), (ndir, bsz, h))
         rh = ctx.buffer((key, "rh"), (ndir, bsz, h))
@@ -217,21 +218,35 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
             # both directions, all positions: ONE launch (csrc/nm_gru_cluster.hip); a hidden size the kernels do not
             # take (300) runs at the next one they do, on zero-padded operands (nn/gru.py: seq_fwd)
             ctx.session.start_deferred_side()      # work that waits for a time loop to hide under (Session.defer_side)
-            ops.zero(states_raw)
-            ops.zero(hcur)
-            gru.seq_fwd(ctx, key, loop_h, slen, ndir, bsz, h, xp, (3 * h, xrs, xts), hcur, hcur, 0, ru_all[0],
-                        ndir * bsz * 2 * h if train else 0, None, 0, c_all[0] if train else None, ndir * bsz * h, wgh,
-                        wch, lengths=len_arg, reverse_dir0=reverse_only, out=states_raw, out_strides=(h, ors, ots))
-        else:
-            ctx.session.start_deferred_side()
-            ctx.session.graphed((key, "fwd_loop", bsz, slen, train), time_loop)
         final_raw = ctx.buffer((key, "final_raw"), (bsz, c_out))
-        for d in range(ndir):
-            ops.copy_cols(hcur[d], final_raw[:, d * h:(d + 1) * h])
+        seq_ops = None          # h_{t-1} and r * h_{t-1} of every position, when the forward loop left them behind
+        if loop_h == h:
+            # the loop starts from h_0 = 0 and writes all of states_raw (zeros past a sentence's length), the final
+            # states where they are read and, when training, the operands of the recurrent kernels' gradients
+            fused = {"final": final_raw}
+            if train:
+                seq_ops = (ctx.buffer((key, "bwd", "hprev"), (bsz, slen, ndir, h)),
+                           ctx.buffer((key, "bwd", "rh_seq"), (bsz, slen, ndir, h)))
+                fused.update(hprev_seq=seq_ops[0], rh_seq=seq_ops[1], seq_strides=(h, ors, ots))
+            gru.seq_fwd(ctx, key, loop_h, slen, ndir, bsz, h, xp, (3 * h, xrs, xts), None, hcur, 0, ru_all[0],
+                        ndir * bsz * 2 * h if train else 0, None, 0, c_all[0] if train else None, ndir * bsz * h, wgh,
+                        wch, lengths=len_arg, reverse_dir0=reverse_only, out=states_raw, out_strides=(h, ors, ots),
+                        **fused)
+        else:
+            if loop_h:      # at a padded hidden size (nn/gru.py): separate passes around the loop
+                ops.zero(hcur)
+                gru.seq_fwd(ctx, key, loop_h, slen, ndir, bsz, h, xp, (3 * h, xrs, xts), hcur, hcur, 0, ru_all[0],
+                            ndir * bsz * 2 * h if train else 0, None, 0, c_all[0] if train else None, ndir * bsz * h, wgh,
+                            wch, lengths=len_arg, reverse_dir0=reverse_only, out=states_raw, out_strides=(h, ors, ots))
+            else:
+                ctx.session.start_deferred_side()
+                ctx.session.graphed((key, "fwd_loop", bsz, slen, train), time_loop)
+            for d in range(ndir):
+                ops.copy_cols(hcur[d], final_raw[:, d * h:(d + 1) * h])
 
         saved = {"x": x, "xp": xp, "ru_all": ru_all, "c_all": c_all, "states_raw": states_raw,
                  "final_raw": final_raw, "lengths": lengths, "wgh": wgh, "wch": wch, "cells": cells,
-                 "ndir": ndir, "h": h, "reverse_only": reverse_only}
+                 "ndir": ndir, "h": h, "reverse_only": reverse_only, "seq_ops": seq_ops}
         if not self.include_final_layer_norm:
             return EncoderActivations(states_raw, final_raw, saved)
         gamma, beta = self.var(ctx, "LayerNorm/gamma"), self.var(ctx, "LayerNorm/beta")
@@ -277,23 +292,26 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
             d_states_raw, d_final_raw = d_states, d_final
 
         # ---- BPTT over the (bi)directional GRU
-        dh = ctx.buffer(key + ("dh",), (ndir, bsz, h), zero=True)
-        if d_final_raw is not None:
+        wgh, wch = sv["wgh"], sv["wch"]
+        loop_h = gru.seq_mode(ctx.session, bsz, h, ndir, wgh, wch)
+        # the cluster loop at the model's own hidden size reads d_final_raw where it lies; every cluster loop writes
+        # all of dxp (zeros past a sentence's length)
+        dh = ctx.buffer(key + ("dh",), (ndir, bsz, h), zero=loop_h != h)
+        if d_final_raw is not None and loop_h != h:
             for d in range(ndir):
                 ops.copy_cols(d_final_raw[:, d * h:(d + 1) * h], dh[d])
-        dxp = ctx.buffer(key + ("dxp",), (bsz * slen, ndir * 3 * h), zero=True)
+        dxp = ctx.buffer(key + ("dxp",), (bsz * slen, ndir * 3 * h), zero=not loop_h)
         dgpre = ctx.buffer(key + ("dgpre",), (2, ndir, bsz, 2 * h))
         dcpre = ctx.buffer(key + ("dcpre",), (ndir, bsz, h))
         drh = ctx.buffer(key + ("drh",), (ndir, bsz, h))
         seq_strides = (h, slen * c_out, c_out)
         dxp_strides = (3 * h, slen * ndir * 3 * h, ndir * 3 * h)
-        wgh, wch = sv["wgh"], sv["wch"]
-        loop_h = gru.seq_mode(ctx.session, bsz, h, ndir, wgh, wch)
         if loop_h:
+            fused = {"fused_io": True, "d_final": d_final_raw} if loop_h == h else {}
             gru.seq_bwd(ctx, id(self), loop_h, slen, ndir, bsz, h, dh, d_states_raw,
                         seq_strides if d_states_raw is not None else None, sv["ru_all"][0], ndir * bsz * 2 * h,
                         sv["c_all"][0], ndir * bsz * h, None, states_raw, seq_strides, dxp, dxp_strides, wgh, wch,
-                        lengths=lengths, reverse_dir0=rev0)
+                        lengths=lengths, reverse_dir0=rev0, **fused)
             from .. import distributed
             if distributed.current() is not None:
                 distributed.current().after_time_loops()
@@ -324,10 +342,13 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
         dxp = self._backward_loop(ctx, sv, d_states, d_final)
 
         # ---- weight gradients, batched over all positions
-        hprev = ctx.buffer(key + ("hprev",), (bsz, slen, ndir, h))
-        rh_seq = ctx.buffer(key + ("rh_seq",), (bsz, slen, ndir, h))
-        ops.gru_seq_shift(states_raw, hprev, lengths, ndir, h, reverse_dir0=rev0)
-        ops.gru_rh_seq(sv["ru_all"], hprev, rh_seq, lengths, ndir, h, reverse_dir0=rev0)
+        if sv.get("seq_ops") is not None:       # the forward cluster loop stored both while it had them in registers
+            hprev, rh_seq = sv["seq_ops"]
+        else:
+            hprev = ctx.buffer(key + ("hprev",), (bsz, slen, ndir, h))
+            rh_seq = ctx.buffer(key + ("rh_seq",), (bsz, slen, ndir, h))
+            ops.gru_seq_shift(states_raw, hprev, lengths, ndir, h, reverse_dir0=rev0)
+            ops.gru_rh_seq(sv["ru_all"], hprev, rh_seq, lengths, ndir, h, reverse_dir0=rev0)
         x2 = x.view(bsz * slen, e)
         hp2, rh2 = hprev.view(bsz * slen, c_out), rh_seq.view(bsz * slen, c_out)
         dx = ctx.buffer(key + ("dx",), (bsz * slen, e))

@@ -84,15 +84,19 @@ def _pad_weights(ctx, key, wgh, wch, h, hp):
 
 
 def seq_fwd(ctx, key, hp, steps, ndir, rows, h, xp, x_strides, h_in0, h_out0, h_step, ru0, ru_step, rh0, rh_step, c0,
-            c_step, wgh, wch, lengths=None, reverse_dir0=False, out=None, out_strides=(0, 0, 0)):
+            c_step, wgh, wch, lengths=None, reverse_dir0=False, out=None, out_strides=(0, 0, 0), **fused):
     """ops.gru_seq_fwd at hidden size ``hp`` (``seq_mode``): directly when hp == h, else on padded copies whose results
-    are copied back into the caller's buffers (the padded gates / candidates / states stay for ``seq_bwd``)."""
+    are copied back into the caller's buffers (the padded gates / candidates / states stay for ``seq_bwd``).  Every
+    position of ``out`` is written either way (zeros past a row's length).  ``fused``: what the loop kernel does itself
+    instead of passes around it (ops.gru_seq_fwd: final, hprev_seq, rh_seq, seq_strides, h0_out; ``h_in0`` None) --
+    at hp == h only, the padded path keeps its separate passes."""
     sticky = ctx.session.error_word()
     if hp == h:
         ops.gru_seq_fwd(steps, ndir, rows, h, xp, x_strides, h_in0, h_out0, h_step, ru0, ru_step, rh0, rh_step, c0, c_step,
                         wgh, wch, cluster_workspace(ctx, key, rows, h, ndir), lengths=lengths, reverse_dir0=reverse_dir0,
-                        out=out, out_strides=out_strides, sticky=sticky)
+                        out=out, out_strides=out_strides, sticky=sticky, zero_padded=out is not None, **fused)
         return
+    assert not fused and h_in0 is not None, "the padded loops keep the separate passes"
     sc = lambda st: st // h * hp
     buf = lambda name, shape, **kw: ctx.buffer((key, "pad", name), shape, **kw)
     wg_p, wc_p = _pad_weights(ctx, key, wgh, wch, h, hp)
@@ -112,13 +116,12 @@ def seq_fwd(ctx, key, hp, steps, ndir, rows, h, xp, x_strides, h_in0, h_out0, h_
     out_p = None
     if out is not None:
         out_p = buf("out", (out.numel() // (ndir * h), ndir * hp))
-        ops.zero(out_p)
     ops.gru_seq_fwd(steps, ndir, rows, hp, xp_p, tuple(sc(v) for v in x_strides), hin_p, hout_p[0],
                     ndir * rows * hp if h_step else 0, ru_p[0], ndir * rows * 2 * hp if ru_step else 0,
                     None if rh_p is None else rh_p[0], ndir * rows * hp if (rh_p is not None and rh_step) else 0,
                     None if c_p is None else c_p[0], ndir * rows * hp if (c_p is not None and c_step) else 0, wg_p, wc_p,
                     cluster_workspace(ctx, key, rows, hp, ndir), lengths=lengths, reverse_dir0=reverse_dir0, out=out_p,
-                    out_strides=tuple(sc(v) for v in out_strides), sticky=sticky)
+                    out_strides=tuple(sc(v) for v in out_strides), sticky=sticky, zero_padded=out_p is not None)
     # back into the caller's buffers (what the rest of the step reads)
     span = lambda t0, n, w: t0.as_strided((n * ndir * rows, w), (w, 1))          # step t at t * ndir * rows rows
     _blocks(span(h_out0, nst, h), hout_p, 1, 1, h, hp, back=True)
@@ -135,14 +138,23 @@ def seq_fwd(ctx, key, hp, steps, ndir, rows, h, xp, x_strides, h_in0, h_out0, h_
 
 
 def seq_bwd(ctx, key, hp, steps, ndir, rows, h, dh, dout, dout_strides, ru0, ru_step, c0, c_step, h0, hseq, hseq_strides,
-            dxp, dxp_strides, wgh, wch, lengths=None, reverse_dir0=False):
-    """ops.gru_seq_bwd at hidden size ``hp``; padded: on the gates / candidates / states ``seq_fwd`` kept."""
+            dxp, dxp_strides, wgh, wch, lengths=None, reverse_dir0=False, fused_io=False, d_final=None):
+    """ops.gru_seq_bwd at hidden size ``hp``; padded: on the gates / candidates / states ``seq_fwd`` kept.  Every
+    position of ``dxp`` is written either way (zeros past a row's length).  ``fused_io`` (hp == h only): dL/dh after the
+    last step is ``d_final`` [R, ndir*h] (None: zero) instead of the contents of ``dh``."""
     sticky = ctx.session.error_word()
     if hp == h:
-        ops.gru_seq_bwd(steps, ndir, rows, h, dh, dout, dout_strides, ru0, ru_step, c0, c_step, h0, hseq, hseq_strides, dxp,
-                        dxp_strides, wgh, wch, cluster_workspace(ctx, key, rows, h, ndir), lengths=lengths,
-                        reverse_dir0=reverse_dir0, sticky=sticky)
+        ws = cluster_workspace(ctx, key, rows, h, ndir)
+        if fused_io:
+            ops.gru_seq_bwd(steps, ndir, rows, h, dh, dout, dout_strides, ru0, ru_step, c0, c_step, h0, hseq, hseq_strides,
+                            dxp, dxp_strides, wgh, wch, ws, lengths=lengths, reverse_dir0=reverse_dir0, sticky=sticky,
+                            fused_io=True, d_final=d_final, zero_padded=True)
+        else:       # dh in place: the extended call reads it where the plain one does, and also zeroes padded dxp
+            ops.gru_seq_bwd(steps, ndir, rows, h, dh, dout, dout_strides, ru0, ru_step, c0, c_step, h0, hseq, hseq_strides,
+                            dxp, dxp_strides, wgh, wch, ws, lengths=lengths, reverse_dir0=reverse_dir0, sticky=sticky,
+                            fused_io=True, d_final=dh.view(ndir * rows, h), d_final_dir=rows * h, zero_padded=True)
         return
+    assert not fused_io, "the padded loops keep the separate passes"
     kept = ctx.memo[(key, "padded_loop")]
     nru, nc, nst = kept["steps_saved"]
     assert nru == steps and nc == steps, "the forward loop did not keep its gates (inference pass?)"
@@ -161,12 +173,12 @@ def seq_bwd(ctx, key, hp, steps, ndir, rows, h, dh, dout, dout_strides, ru0, ru_
         _blocks(dout, dout_p, ndir, 1, h, hp)
     n_x = dxp.numel() // (ndir * 3 * h)
     dxp_p = buf("dxp", (n_x, ndir * 3 * hp))
-    ops.zero(dxp_p)
     ops.gru_seq_bwd(steps, ndir, rows, hp, dh_p, dout_p, None if dout is None else tuple(sc(v) for v in dout_strides),
                     kept["ru"][0], ndir * rows * 2 * hp, kept["c"][0], ndir * rows * hp, None if h0 is None else kept["h_in"],
                     hseq_p, tuple(sc(v) for v in hseq_strides), dxp_p, tuple(sc(v) for v in dxp_strides), kept["wg"],
                     kept["wc"], cluster_workspace(ctx, key, rows, hp, ndir), lengths=lengths, reverse_dir0=reverse_dir0,
-                    sticky=sticky)
+                    sticky=sticky, fused_io=True, d_final=dh_p.view(ndir * rows, hp), d_final_dir=rows * hp,
+                    zero_padded=True)
     _blocks(dxp, dxp_p, ndir, 3, h, hp, back=True)
     _blocks(dh, dh_p, 1, 1, h, hp, back=True)
 

@@ -1171,38 +1171,71 @@ def _cluster_serialize_after(stream):
 
 def gru_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, ru0, ru_step, rh0, rh_step, c0,
                 c_step, wgh, wch, workspace, lengths=None, reverse_dir0=False, out=None, out_strides=(0, 0, 0),
-                sticky=None):
+                sticky=None, zero_padded=False, final=None, hprev_seq=None, rh_seq=None, seq_strides=None, h0_out=None):
     """All ``steps`` forward GRU steps in one launch (nm_gru_seq_fwd: workgroup clusters, csrc/nm_gru_cluster.hip).
     Tensors of step t: h_out0 + t*h_step etc. (element strides); ``rh0`` may be None; wgh [ndir,H,2H], wch [ndir,H,H]
     (2-D accepted for ndir 1); ``workspace`` from ``gru_seq_workspace``; ``sticky``: an int32 device word that a launch
-    which gave up waiting sets to 1 (runtime.Session.error_word)."""
+    which gave up waiting sets to 1 (runtime.Session.error_word).
+
+    What the loop does itself when asked (nm_gru_seq_fwd_ex): ``h_in0`` None: h_0 = 0; ``zero_padded``: zeros at the
+    positions of ``out`` past a row's length; ``final`` [R, ndir*H] (row stride free): the state after each row's last
+    valid step; ``hprev_seq`` / ``rh_seq`` with ``seq_strides`` (dir, row, time): h_{t-1} and r * h_{t-1} by position,
+    zeros when padded; ``h0_out`` [ndir,R,H]: a copy of the initial state."""
     lib = _lib.load()
+    io = None
+    if h_in0 is None or zero_padded or final is not None or hprev_seq is not None or rh_seq is not None or \
+            h0_out is not None:
+        io = _lib.GruSeqIo()
+        io.zero_padded = int(bool(zero_padded))
+        if final is not None:
+            assert final.dim() == 2 and final.stride(1) == 1
+            io.final_state, io.final_row, io.final_dir = final.data_ptr(), final.stride(0), hsz
+        io.hprev_seq, io.rh_seq = _p(hprev_seq), _p(rh_seq)
+        io.seq_dir, io.seq_row, io.seq_time = seq_strides or (0, 0, 0)
+        io.h0_out = _p(h0_out)
     e = _lib.GruEpilogue()
     e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 1, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
     e.lengths = _p(lengths)
     e.xp = xp.data_ptr()
     e.x_dir, e.x_row, e.x_time = x_strides
-    e.h_in, e.h_out, e.ru, e.rh, e.c_save, e.out = (h_in0.data_ptr(), h_out0.data_ptr(), ru0.data_ptr(),
+    e.h_in, e.h_out, e.ru, e.rh, e.c_save, e.out = (_p(h_in0), h_out0.data_ptr(), ru0.data_ptr(),
                                                    _p(rh0), _p(c0), _p(out))
     e.o_dir, e.o_row, e.o_time = out_strides
     g2 = wgh[0] if wgh.dim() == 3 else wgh
     c2 = wch[0] if wch.dim() == 3 else wch
     assert g2.stride(1) == 1 and c2.stride(1) == 1
     serial = _cluster_serialize_before()
-    _lib.check(lib.nm_gru_seq_fwd(_stream(), ctypes.byref(e), steps, h_step, ru_step, rh_step, c_step,
-                                  wgh.data_ptr(), g2.stride(0), wgh.stride(0) if wgh.dim() == 3 else 0,
-                                  wch.data_ptr(), c2.stride(0), wch.stride(0) if wch.dim() == 3 else 0,
-                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky)),
-               "nm_gru_seq_fwd")
+    tail = (steps, h_step, ru_step, rh_step, c_step,
+            wgh.data_ptr(), g2.stride(0), wgh.stride(0) if wgh.dim() == 3 else 0,
+            wch.data_ptr(), c2.stride(0), wch.stride(0) if wch.dim() == 3 else 0,
+            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky))
+    if io is None:
+        _lib.check(lib.nm_gru_seq_fwd(_stream(), ctypes.byref(e), *tail), "nm_gru_seq_fwd")
+    else:
+        _lib.check(lib.nm_gru_seq_fwd_ex(_stream(), ctypes.byref(e), ctypes.byref(io), *tail), "nm_gru_seq_fwd_ex")
     _cluster_serialize_after(serial)
 
 
 def gru_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, c0, c_step, h0, hseq, hseq_strides,
-                dxp, dxp_strides, wgh, wch, workspace, lengths=None, reverse_dir0=False, sticky=None):
+                dxp, dxp_strides, wgh, wch, workspace, lengths=None, reverse_dir0=False, sticky=None, fused_io=False,
+                d_final=None, d_final_dir=None, zero_padded=False):
     """The whole BPTT loop in one launch (nm_gru_seq_bwd): ``dh`` [ndir,R,H] holds dL/dh after the last step on entry
     and dL/dh_0 on exit; ``ru0`` / ``c0`` are the gates / candidates of step 0 (step t at + t*step elements);
-    pre-activation gradients land in ``dxp``; wgh [ndir,H,2H], wch [ndir,H,H] (2-D accepted for ndir 1)."""
+    pre-activation gradients land in ``dxp``; wgh [ndir,H,2H], wch [ndir,H,H] (2-D accepted for ndir 1).
+
+    ``fused_io`` (nm_gru_seq_bwd_ex): dL/dh after the last step is ``d_final`` [R, ndir*H] (row stride free; None: zero)
+    and ``dh`` is only written (``d_final_dir``: element offset of a direction's block, default H); ``zero_padded``: zeros at the positions of ``dxp`` past a row's length."""
     lib = _lib.load()
+    io = None
+    if fused_io:
+        io = _lib.GruSeqIo()
+        io.zero_padded = int(bool(zero_padded))
+        if d_final is not None:
+            assert d_final.dim() == 2 and d_final.stride(1) == 1
+            io.d_final, io.dfinal_row = d_final.data_ptr(), d_final.stride(0)
+            io.dfinal_dir = hsz if d_final_dir is None else d_final_dir
+    else:
+        assert d_final is None and not zero_padded
     e = _lib.GruEpilogue()
     e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 4, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
     e.lengths = _p(lengths)
@@ -1216,11 +1249,14 @@ def gru_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, c0
     c2 = wch[0] if wch.dim() == 3 else wch
     assert g2.stride(1) == 1 and c2.stride(1) == 1
     serial = _cluster_serialize_before()
-    _lib.check(lib.nm_gru_seq_bwd(_stream(), ctypes.byref(e), steps, ru_step, c_step,
-                                  wgh.data_ptr(), g2.stride(0), wgh.stride(0) if wgh.dim() == 3 else 0,
-                                  wch.data_ptr(), c2.stride(0), wch.stride(0) if wch.dim() == 3 else 0,
-                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky)),
-               "nm_gru_seq_bwd")
+    tail = (steps, ru_step, c_step,
+            wgh.data_ptr(), g2.stride(0), wgh.stride(0) if wgh.dim() == 3 else 0,
+            wch.data_ptr(), c2.stride(0), wch.stride(0) if wch.dim() == 3 else 0,
+            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky))
+    if io is None:
+        _lib.check(lib.nm_gru_seq_bwd(_stream(), ctypes.byref(e), *tail), "nm_gru_seq_bwd")
+    else:
+        _lib.check(lib.nm_gru_seq_bwd_ex(_stream(), ctypes.byref(e), ctypes.byref(io), *tail), "nm_gru_seq_bwd_ex")
     _cluster_serialize_after(serial)
 
 
