@@ -222,6 +222,13 @@ GRU_SEQ_SIGNATURES = {
     "nm_gru_seq_bwd_ex": (I, [P, P, P, ctypes.c_int32, L, L, P, L, L, P, L, L, P, L, P]),
 }
 
+# ... and every symbol include/nmhip_subword.h declares (the reward of ReinforceObjective over subword pieces,
+# csrc/nm_subword.hip)
+SUBWORD_SIGNATURES = {
+    "nm_eval_joined_sentence_score_max_tokens": (L, []),
+    "nm_eval_joined_sentence_score": (I, [P, I, I, P, L, L, P, L, L, L, P, L, L, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -292,7 +299,7 @@ def load():
                               + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
                               + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
                               + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
-                              + list(GRU_SEQ_SIGNATURES.items())):
+                              + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

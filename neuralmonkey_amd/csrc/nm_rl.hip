@@ -10,11 +10,12 @@
 //                              over the REFERENCE's start positions (the count is "reference windows that occur in the
 //                              hypothesis") and walk the hypothesis serially -- every lane reads the same LDS words, a
 //                              broadcast; the longest common prefix, capped at 4, answers all orders at once.  Integer
-//                              counts, 64-wide shuffles, no atomics; lane 0 finishes in double and rounds once.
+//                              counts, 64-wide shuffles, no atomics; lane 0 finishes in double (nm_score.h) and rounds once.
 //   rl_sample_weights_kernel   one workgroup: the sum of the rewards (float32, eight interleaved partial sums on one
 //                              lane) and the baseline's state, one thread per sentence for the softmax over the
 //                              sample axis, then all threads spread the coefficients over the time axis.
 #include "nm_common.h"
+#include "nm_score.h"
 #include "../../include/nmhip_rl.h"
 
 namespace {
@@ -90,35 +91,7 @@ __global__ __launch_bounds__(64) void eval_score_kernel(
     for (int k = 0; k < 4; ++k) tp[k] = eval_wave_sum(tp[k]);
     if (lane != 0) return;
 
-    double score;
-    if (kind == 1) {
-        long sum_tp = 0, sum_gen = 0, sum_tgt = 0;           // |hyp|, |ref| >= 1: neither total is 0
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < order) {
-                sum_tp += tp[k];
-                sum_gen += max(0, Lh - k);
-                sum_tgt += max(0, Lr - k);
-            }
-        score = fmin((double)sum_tp / (double)sum_tgt, (double)sum_tp / (double)sum_gen);
-    } else {
-        const double weight = 1.0 / (double)order;
-        double log_bleu = 0.0, smooth = 1.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < order) {
-                const int gen = max(0, Lh - k);
-                double prec = gen == 0 ? 1.0 : (double)tp[k] / (double)gen;
-                if (prec == 0.0) {
-                    smooth *= 2.0;
-                    prec = 1.0 / (smooth * (double)gen);
-                }
-                log_bleu += weight * log(prec);
-            }
-        log_bleu += fmin(1.0 - (double)Lr / (double)Lh, 0.0);
-        score = 100.0 * exp(log_bleu);
-    }
-    out[b] = (float)score;
+    out[b] = (float)nm_eval_finish(kind, order, tp, Lr, Lh);
 }
 
 // The sum of every thread's `v` in a fixed order, handed to every thread.

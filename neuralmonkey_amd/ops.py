@@ -2114,6 +2114,40 @@ def eval_sentence_score(kind, order, references, hypotheses, end_id, pad_id, out
     return out
 
 
+# ---- ... over a vocabulary of subword pieces (include/nmhip_subword.h, csrc/nm_subword.hip) ----------------------------------
+PIECE_TABLE_ROW = 12
+
+
+def eval_joined_sentence_score_max_tokens() -> int:
+    return int(_lib.load().nm_eval_joined_sentence_score_max_tokens())
+
+
+def eval_joined_sentence_score(kind, order, references, hypotheses, table, out=None):
+    """``eval_sentence_score`` over the indices of subword PIECES: the words compared are those of the reference's join
+    (trainers/rl_trainer.py:110-111), each identified by its length in bytes and two polynomial hashes composed from
+    the rows of ``table`` -- int32 [V, 12] on the device, ``trainers.rl_trainer.piece_table`` of the vocabulary.
+    ``references`` [T_ref, B] and ``hypotheses`` [T_hyp, B] are int32, time-major, with unit batch stride and any row
+    stride, each cut at its first token the table flags as ``</s>`` or ``<pad>`` (or whose id is outside the table)."""
+    lib = _lib.load()
+    _i32(references), _i32(hypotheses), _i32(table)
+    assert references.dim() == 2 and hypotheses.dim() == 2 and references.shape[1] == hypotheses.shape[1]
+    assert table.dim() == 2 and table.shape[1] == PIECE_TABLE_ROW and table.is_contiguous()
+    assert table.device == references.device == hypotheses.device
+    bsz = references.shape[1]
+    strides = []
+    for t in (references, hypotheses):
+        assert bsz == 1 or t.stride(1) == 1, "unit batch stride"
+        strides.append(t.stride(0) if t.shape[0] > 1 else max(t.stride(0), bsz))
+    if out is None:
+        out = torch.empty(bsz, dtype=torch.float32, device=references.device)
+    assert _f32(out).numel() == bsz and out.is_contiguous()
+    _lib.check(lib.nm_eval_joined_sentence_score(_stream(), REWARD_KINDS[kind], int(order), references.data_ptr(),
+                                                 strides[0], references.shape[0], hypotheses.data_ptr(), strides[1],
+                                                 hypotheses.shape[0], bsz, table.data_ptr(), table.shape[0],
+                                                 table.shape[0], out.data_ptr()), "nm_eval_joined_sentence_score")
+    return out
+
+
 def reinforce_sample_weights(rewards, sent_logprobs, steps, weights, grad_scale, loss, baseline, weight=1.0,
                              subtract_baseline=False, normalize=False, alpha=1.0, reward_counter=None, reward_sum=None):
     """trainers/rl_trainer.py:149-185 in one launch: from ``rewards`` and ``sent_logprobs`` [S, B], the host list

@@ -14,8 +14,12 @@ MI355X mapping: the reference calls an evaluator object once per sentence and pe
 ``GLEUEvaluator`` / ``BLEUEvaluator`` over a vocabulary whose words are whole words scores all sentences of a sample in ONE
 launch on token indices (``nm_eval_sentence_score``), ``nm_reinforce_sample_weights`` turns rewards, sentence
 log-probabilities and the baseline's two device scalars into the row weights and the scalar of ``nm_xent`` over every
-sample's taped logits, whose gradient is written in place; after the sampling loops the step reads nothing back.  Any
-other callable gets the reference's treatment: indices to strings, the BPE join, one call per sentence on the host.
+sample's taped logits, whose gradient is written in place; after the sampling loops the step reads nothing back.  Over
+a vocabulary of subword PIECES (words that end with "@@") the same evaluators run in one launch too
+(``nm_eval_joined_sentence_score``): a joined word is its length in bytes and two polynomial hashes composed on the
+device from a per-vocabulary table (``piece_table``), so there equality of words is equality of (length, hash) -- see
+include/nmhip_subword.h for the collision bound.  Any other callable gets the reference's treatment: indices to
+strings, the BPE join, one call per sentence on the host.
 """
 import warnings
 from typing import Callable, List, Optional
@@ -55,6 +59,92 @@ def words_are_indices(vocabulary) -> bool:
         cached = (len(vocabulary), plain)
         vocabulary._words_are_indices = cached             # pylint: disable=protected-access
     return cached[1]
+
+
+# the two polynomial hashes of a joined word (include/nmhip_subword.h): H(s) = sum_i (byte_i + 1) * P^(len - 1 - i) mod M
+PIECE_MODULI = (2147483647, 2147483629)                  # 2^31 - 1 and 2^31 - 19, primes
+PIECE_BASES = (1103515245, 1664525)
+PIECE_CONTINUES, PIECE_CUTS = 1, 2                       # the flags of a table row
+
+
+def _piece_element(text: str) -> tuple:
+    """(hash mod M1, hash mod M2, P1^len mod M1, P2^len mod M2, len) of the UTF-8 bytes of ``text``."""
+    data = text.encode("utf-8")
+    out = []
+    for modulus, base in zip(PIECE_MODULI, PIECE_BASES):
+        value = 0
+        for byte in data:
+            value = (value * base + byte + 1) % modulus
+        out.append(value)
+    return (out[0], out[1], pow(PIECE_BASES[0], len(data), PIECE_MODULI[0]),
+            pow(PIECE_BASES[1], len(data), PIECE_MODULI[1]), len(data))
+
+
+def _compose(left: tuple, right: tuple) -> tuple:
+    """The element of ``left`` followed by ``right``: H(s + t) = H(s) * P^len(t) + H(t)."""
+    (m1, m2) = PIECE_MODULI
+    return ((left[0] * right[2] + right[0]) % m1, (left[1] * right[3] + right[1]) % m2, left[2] * right[2] % m1,
+            left[3] * right[3] % m2, left[4] + right[4])
+
+
+def piece_table(vocabulary) -> Optional[np.ndarray]:
+    """The table of ``ops.eval_joined_sentence_score``: int32 [V, 12], per entry the element of the stem (the text without
+    a trailing "@@"), the element of the whole text, the flags (continuation piece, ``</s>`` or ``<pad>`` BY STRING: a
+    vocabulary may repeat a word) and 0.  ``None`` for a vocabulary with an empty word or a word that holds a space, where
+    the reference's join is not the rule the kernel applies.  Computed once per vocabulary."""
+    cached = getattr(vocabulary, "_piece_table", None)
+    if cached is None or cached[0] != len(vocabulary):
+        words = list(vocabulary.index_to_word)
+        table = None
+        if all(w and " " not in w for w in words):
+            table = np.zeros((len(words), ops.PIECE_TABLE_ROW), np.int32)
+            for row, word in zip(table, words):
+                continues = word.endswith("@@")
+                row[0:5] = _piece_element(word[:-2] if continues else word)
+                row[5:10] = _piece_element(word)
+                row[10] = (PIECE_CONTINUES if continues else 0) | (PIECE_CUTS if word in (END_TOKEN, PAD_TOKEN) else 0)
+        cached = (len(vocabulary), table, {})
+        vocabulary._piece_table = cached                    # pylint: disable=protected-access
+    return cached[1]
+
+
+def device_piece_table(vocabulary, device) -> torch.Tensor:
+    """``piece_table`` on ``device``, copied there once per (vocabulary, device)."""
+    table = piece_table(vocabulary)
+    on_devices = vocabulary._piece_table[2]                 # pylint: disable=protected-access
+    key = str(torch.device(device))
+    if key not in on_devices:
+        on_devices[key] = torch.from_numpy(table).to(device)
+    return on_devices[key]
+
+
+def joined_word_keys(vocabulary, column) -> List[tuple]:
+    """The keys (bytes, hash mod M1, hash mod M2) of the joined words of one column of piece indices, from the rows of
+    ``piece_table`` alone -- what the kernel computes, stated on the host: the cut at the first flagged token, a
+    continuation piece with a kept token behind it lends its stem to the next word, every other kept token ends a word
+    with its whole text; an empty column is the one word of no bytes."""
+    table = piece_table(vocabulary)
+    kept = []
+    for index in column:
+        if not 0 <= index < len(table) or table[index][10] & PIECE_CUTS:
+            break
+        kept.append(int(index))
+    keys, open_word = [], (0, 0, 1, 1, 0)
+    for position, index in enumerate(kept):
+        row = [int(v) for v in table[index]]
+        if row[10] & PIECE_CONTINUES and position != len(kept) - 1:
+            open_word = _compose(open_word, tuple(row[0:5]))
+        else:
+            done = _compose(open_word, tuple(row[5:10]))
+            keys.append((done[4], done[0], done[1]))
+            open_word = (0, 0, 1, 1, 0)
+    return keys or [(0, 0, 0)]
+
+
+def word_key(word: str) -> tuple:
+    """The key of one joined word, from its characters."""
+    element = _piece_element(word)
+    return (element[4], element[0], element[1])
 
 
 def score_on_the_host(vocabulary, reward_function, references: np.ndarray, hypotheses: np.ndarray) -> np.ndarray:
@@ -113,27 +203,43 @@ class ReinforceObjective(Objective):
             store.declare(name, (), zeros_initializer(), trainable=False)
 
     # -- rewards ------------------------------------------------------------------------------------------------
-    def device_reward(self) -> Optional[tuple]:
-        """(kind, order) when the reward runs as ``ops.eval_sentence_score``: a GLEU or BLEU evaluator proper, without
-        de-duplication, BLEU with one reference, orders up to 4, over a vocabulary of whole words.  (A BPE vocabulary
-        needs a hash per joined word -- two piece sequences can spell one word -- and takes the host route.)"""
+    def evaluator_reward(self) -> Optional[tuple]:
+        """(kind, order) when the reward is one the kernels compute: a GLEU or BLEU evaluator proper, without
+        de-duplication, BLEU with one reference, orders up to 4."""
         fn = self.reward_function
         if type(fn) not in (GLEUEvaluator, BLEUEvaluator) or fn.deduplicate or not 1 <= fn.n <= 4:
             return None
         if isinstance(fn, BLEUEvaluator) and fn.multiple_references_separator is not None:
             return None
-        if not words_are_indices(self.decoder.vocabulary):
-            return None
         return ("bleu" if isinstance(fn, BLEUEvaluator) else "gleu"), fn.n
 
+    def device_reward(self) -> Optional[tuple]:
+        """(kind, order) when the reward runs as ``ops.eval_sentence_score``: an evaluator of ``evaluator_reward`` over a
+        vocabulary of whole words, where equal words are equal indices."""
+        if not words_are_indices(self.decoder.vocabulary):
+            return None
+        return self.evaluator_reward()
+
+    def joined_device_reward(self) -> Optional[tuple]:
+        """(kind, order) when the reward runs as ``ops.eval_joined_sentence_score``: the same evaluators over any
+        vocabulary that has a ``piece_table`` -- a BPE vocabulary, where two piece sequences can spell one word and the
+        kernel compares (length, hash) of the joined words."""
+        if piece_table(self.decoder.vocabulary) is None:
+            return None
+        return self.evaluator_reward()
+
     def rewards(self, ctx, references: torch.Tensor, hypotheses: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        """One float32 per sentence into ``out`` [B] on the device.  The evaluators of ``device_reward``: one kernel
-        launch.  Anything else: the reference's ``tf.py_func`` -- both arrays to the host (a synchronisation), one call
-        per sentence, the result back."""
+        """One float32 per sentence into ``out`` [B] on the device.  The evaluators of ``device_reward`` and, over
+        subword pieces, of ``joined_device_reward``: one kernel launch.  Anything else: the reference's ``tf.py_func``
+        -- both arrays to the host (a synchronisation), one call per sentence, the result back."""
         on_device = self.device_reward()
         if on_device is not None and references.is_cuda:
             return ops.eval_sentence_score(on_device[0], on_device[1], references, hypotheses, END_TOKEN_INDEX,
                                            PAD_TOKEN_INDEX, out=out)
+        joined = self.joined_device_reward()
+        if joined is not None and references.is_cuda:
+            table = device_piece_table(self.decoder.vocabulary, references.device)
+            return ops.eval_joined_sentence_score(joined[0], joined[1], references, hypotheses, table, out=out)
         host = score_on_the_host(self.decoder.vocabulary, self.reward_function, references.cpu().numpy(),
                                  hypotheses.cpu().numpy().astype(np.int64))
         return out.copy_(torch.from_numpy(np.ascontiguousarray(host.reshape(out.shape))))
