@@ -229,6 +229,15 @@ SUBWORD_SIGNATURES = {
     "nm_eval_joined_sentence_score": (I, [P, I, I, P, L, L, P, L, L, L, P, L, L, P]),
 }
 
+# ... and every symbol include/nmhip_bnsync.h declares (batch norm with statistics over all ranks of a data-parallel
+# job, csrc/nm_bnsync.hip)
+BNSYNC_SIGNATURES = {
+    "nm_bn2d_part_stats": (I, [P, P, L, L, L, P]),
+    "nm_bn2d_merge": (I, [P, P, L, L, F, P, P, P, P, P]),
+    "nm_bn2d_bwd_sums": (I, [P, P, L, P, L, P, L, L, L, P, P, F, I, P, P, P, I]),
+    "nm_bn2d_bwd_dx": (I, [P, P, L, P, L, P, L, L, L, P, P, P, F, I, P, L, P, L, I]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -299,7 +308,8 @@ def load():
                               + list(LABEL_SIGNATURES.items()) + list(POOL_SIGNATURES.items())
                               + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
                               + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
-                              + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())):
+                              + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
+                              + list(BNSYNC_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

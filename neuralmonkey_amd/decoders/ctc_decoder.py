@@ -145,16 +145,15 @@ class CTCDecoder(ModelPart):
         return ops.ctc_mask_lengths(mask, out)
 
     # -- the interface GenericTrainer._objective_gradients calls ----------------------------------------
+    # The cost is a plain sum over the sentences, not a mean over target tokens.  GenericTrainer._objective_gradients
+    # reads this: the gradient scale is the objective's weight on every rank, with no count summed over the ranks
+    # (that sum, 1 per rank, would divide the gradient by the number of ranks).  Under data parallelism every rank
+    # back-propagates its own sentences' sum, the gradient exchange adds the ranks' gradients up to the gradient of the
+    # full batch's sum, and a fetched ``cost`` is the RANK'S OWN sum (the full batch's cost is the sum over ranks).
+    loss_is_batch_sum = True
+
     def train_token_count(self, ctx) -> float:
         """The cost is a plain sum over the batch: the trainer's ``weight / count`` scale is the objective's weight."""
-        from .. import distributed as dist
-        dp = dist.current()
-        if dp is not None and dp.world_size > 1:
-            raise NotImplementedError(
-                "CTCDecoder '{}' under data parallelism: the trainer divides every objective's gradient by the "
-                "GLOBAL token count summed over the ranks, which for this summed loss (count 1 per rank) would divide "
-                "by the number of ranks; a summed-loss path through distributed.scale_by_global_count is not "
-                "implemented".format(self.name))
         return 1.0
 
     def _forward(self, ctx, want_grad: bool, grad_scale: Optional[torch.Tensor], tag: str, with_loss: bool):

@@ -25,6 +25,10 @@ updated parameter slices.  The update every replica ends up with is the referenc
 tensor, one identical step everywhere); replicas are bit-identical by construction -- each
 element is updated once, by its owner, and copied.  The optimizer slots are valid on
 their owners only (``gather_optimizer_slots`` before a checkpoint).
+
+Model parts whose forward pass needs more than their own shard exchange inside the pass: batch normalisation takes its
+statistics over all ranks' rows (``gather_parts`` forward, ``sum_small`` backward: image_ops.batch_norm2d), two small
+collectives per layer and step, in the tape's program order on every rank and never inside a captured step graph.
 """
 import os
 from typing import Optional
@@ -123,6 +127,7 @@ class DataParallel:
         self.poison_foreign = False            # tests: after a reduction, what this rank does not own reads NaN
         self.optimizer_ms: list = []
         self.gather_bytes_per_step = 0
+        self._pinned: list = []                # pinned host doubles of ``read_later``, free for reuse
         self._sparse_bufs: dict = {}
         self.sparse_bytes_per_step = 0
         self._handles: list = []          # collectives in flight this step
@@ -211,6 +216,53 @@ class DataParallel:
         t = torch.full((1,), float(count), dtype=torch.float64, device=scale.device)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)                  # the stream waits for it, the host does not
         scale.copy_(torch.where(t > 0, float(weight) / t.clamp_min(1.0), torch.zeros_like(t)).to(scale.dtype))
+
+    # -- small exchanges inside the forward / backward pass (image_ops.batch_norm2d) -----------------------------------
+    # Every rank calls them in the same program order; none may run inside a captured step graph.
+    def gather_parts(self, part: torch.Tensor) -> torch.Tensor:
+        """[world, len(part)]: the small device vector ``part`` of every rank, in rank order, on every rank, ordered on
+        the current stream.  gloo has no all-gather of device tensors, so this is the all-reduce of a zeroed buffer in
+        which each rank fills its own row: every entry has ONE non-zero contributor, the sum is exact on any backend."""
+        out = torch.zeros((self.world_size, part.numel()), dtype=part.dtype, device=part.device)
+        out[self.rank].copy_(part.reshape(-1))
+        if self.world_size > 1 or self.forced:
+            dist.all_reduce(out, op=dist.ReduceOp.SUM)
+        return out
+
+    def sum_small(self, vec: torch.Tensor) -> torch.Tensor:
+        """In-place sum over the ranks of a small device vector.  RCCL: enqueued behind the current stream, which waits
+        for it -- the host does not (as ``scale_by_global_count``).  Other backends: the sum is taken on the host."""
+        if self.world_size == 1 and not self.forced:
+            return vec
+        if dist.get_backend() == "nccl" and vec.is_cuda:
+            dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+            return vec
+        host = vec.detach().cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self._host_group)
+        vec.copy_(host)
+        return vec
+
+    def read_later(self, value: torch.Tensor):
+        """-> a function that hands back the device scalar ``value`` (as of now) as a Python float.  The copy to pinned
+        host memory is enqueued now; the function waits for that copy alone, not for what was enqueued after it, so a
+        reader in the backward pass (batch norm's global row count) does not drain the stream."""
+        if not value.is_cuda:
+            number = float(value.item())
+            return lambda: number
+        assert value.dtype == torch.float64 and value.numel() == 1
+        slot = self._pinned.pop() if self._pinned else torch.empty(1, dtype=torch.float64).pin_memory()
+        slot.copy_(value.reshape(1), non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        box: list = []
+
+        def read() -> float:
+            if not box:
+                done.synchronize()
+                box.append(float(slot.item()))
+                self._pinned.append(slot)          # (free for the next reader)
+            return box[0]
+        return read
 
     def _wait_handles(self) -> None:
         """The current stream waits for every collective of the step enqueued so far."""

@@ -167,7 +167,10 @@ class CNNEncoder(ModelPart, SpatialStatefulWithOutput):
 
     def graph_safe_training(self, train_mode: bool) -> bool:
         """The forward pass of a training step writes the moving statistics: a replay would be correct, but the step
-        is not worth a graph (a dozen launches), and the images are staged from the host on every step anyway."""
+        is not worth a graph (a dozen launches), and the images are staged from the host on every step anyway.
+        Under data parallelism it MUST stay False: every batch-norm layer then exchanges its statistics (forward) and its
+        two channel sums (backward) with the other ranks (image_ops.batch_norm2d), the backward pass waits on the host
+        for the global row count, and neither a collective nor a host wait may land inside a captured step graph."""
         return False
 
     # -- variables ---------------------------------------------------------------------------------------------
@@ -259,11 +262,6 @@ class CNNEncoder(ModelPart, SpatialStatefulWithOutput):
 
     @tensor
     def _activations(self, ctx):
-        from .. import distributed as dist
-        dp = dist.current()
-        if self.batch_normalize and dp is not None and dp.world_size > 1:
-            raise NotImplementedError("CNNEncoder '{}': batch normalisation under data parallelism over {} ranks would "
-                                      "need statistics over all ranks' batches".format(self.name, dp.world_size))
         train = bool(ctx.fed(self.train_mode))
         images = self.image_input_tensor(ctx)
         mask = self.image_mask(ctx)

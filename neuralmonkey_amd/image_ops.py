@@ -57,7 +57,14 @@ def batch_norm2d(tape: Tape, x: Var, gamma: Var, beta: Var, moving_mean: torch.T
     (cnn_encoder.py:107), and the ReLU that follows it everywhere but in ``project_input`` (nm_bn2d_fwd).  Training:
     the batch's mean and biased variance, kept for the backward pass; ``update_moving``: the moving statistics take
     their step (what the trainers' UPDATE_OPS fetch does, generic_trainer.py:250).  Inference: the moving statistics.
-    -> (y, (batch mean, batch variance) -- None, None in inference).  Backward (training mode only): nm_bn2d_bwd."""
+    -> (y, (batch mean, batch variance) -- None, None in inference).  Backward (training mode only): nm_bn2d_bwd.
+
+    Training under data parallelism (a ``distributed.DataParallel`` of several ranks, or a forced one, is current): the
+    statistics are those of ALL ranks' rows -- ``_batch_norm2d_over_ranks``.  Inference never exchanges anything."""
+    from . import distributed
+    dp = distributed.current()
+    if training and dp is not None and (dp.world_size > 1 or dp.forced):
+        return _batch_norm2d_over_ranks(tape, dp, x, gamma, beta, moving_mean, moving_var, relu, update_moving)
     c = x.shape[1]
     out = tape.new(tuple(x.shape))
     mean = tape.buf((c,)) if training else None
@@ -75,6 +82,42 @@ def batch_norm2d(tape: Tape, x: Var, gamma: Var, beta: Var, moving_mean: torch.T
         ops.bn2d_bwd(x.data, out.data if relu else None, out.grad, gamma.data, mean, var, relu, tape.buf((2 * c,)),
                      dx=gx, accumulate_dx=acc, dgamma=tape.grad(gamma) if gamma.needs_grad else None,
                      dbeta=tape.grad(beta) if beta.needs_grad else None, accumulate_params=True)
+    tape.record(bwd)
+    return out, (mean, var)
+
+
+def _batch_norm2d_over_ranks(tape: Tape, dp, x: Var, gamma: Var, beta: Var, moving_mean: torch.Tensor,
+                             moving_var: torch.Tensor, relu: bool, update_moving: bool):
+    """Training-mode ``batch_norm2d`` whose batch is dealt over the ranks of ``dp`` (include/nmhip_bnsync.h); the ranks'
+    row counts may differ.  Forward: nm_bn2d_part_stats -> the parts of all ranks gathered -> nm_bn2d_merge (every rank
+    merges the same parts in rank order: identical batch and moving statistics everywhere) -> nm_bn2d_fwd in inference
+    mode on the merged statistics.  Backward: nm_bn2d_bwd_sums (dgamma / dbeta take the rank's OWN sums: the gradient
+    exchange adds the ranks' up) -> the [2C] sums added over the ranks -> nm_bn2d_bwd_dx with the global row count.
+    Two exchanges per layer and step, issued where the tape stands: every rank runs the same tape in the same order."""
+    c = x.shape[1]
+    out = tape.new(tuple(x.shape))
+    mean, var = tape.buf((c,)), tape.buf((c,))
+    part = tape.buf((ops.bn2d_part_doubles(c),), torch.float64)
+    total = tape.buf((1,), torch.float64)
+    ops.bn2d_part_stats(x.data, part)
+    ops.bn2d_merge(dp.gather_parts(part), mean, var, total, moving_mean=moving_mean if update_moving else None,
+                   moving_var=moving_var if update_moving else None)
+    ops.bn2d_fwd(x.data, gamma.data, beta.data, out.data, False, relu, moving_mean=mean, moving_var=var)
+    rows = dp.read_later(total) if tape.recording else None      # (the backward pass needs the count on the host)
+
+    def bwd():
+        if out.grad is None:
+            return
+        sums = tape.buf((2 * c,))
+        ops.bn2d_bwd_sums(x.data, out.data if relu else None, out.grad, mean, var, relu, sums,
+                          dgamma=tape.grad(gamma) if gamma.needs_grad else None,
+                          dbeta=tape.grad(beta) if beta.needs_grad else None, accumulate_params=True)
+        if not x.needs_grad:
+            return
+        dp.sum_small(sums)
+        gx, acc = tape.grad_slot(x)
+        ops.bn2d_bwd_dx(x.data, out.data if relu else None, out.grad, gamma.data, mean, var, relu, sums, int(rows()), gx,
+                        accumulate_dx=acc)
     tape.record(bwd)
     return out, (mean, var)
 

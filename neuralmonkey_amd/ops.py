@@ -2005,6 +2005,71 @@ def bn2d_bwd(x, y, dy, gamma, batch_mean, batch_var, relu, sums, dx=None, accumu
                                        int(bool(accumulate_params)), sums.data_ptr()), "nm_bn2d_bwd")
 
 
+# the same batch norm with statistics over the rows of all ranks (include/nmhip_bnsync.h, csrc/nm_bnsync.hip)
+def bn2d_part_doubles(c) -> int:
+    """Doubles of one rank's part: the row count, C means, C sums of squared deviations."""
+    return 2 * int(c) + 1
+
+
+def _f64(t):
+    assert t.dtype == torch.float64 and t.is_cuda, (t.dtype, t.device)
+    return t
+
+
+def bn2d_part_stats(x, part):
+    """This rank's part of the statistics of x [rows, C] into ``part`` (float64 [2C + 1]) (nm_bn2d_part_stats)."""
+    c = x.shape[1]
+    ldx = _ld2(x, c, "bn2d_part_stats x")
+    assert _f64(part).is_contiguous() and part.numel() == bn2d_part_doubles(c)
+    _lib.check(_lib.load().nm_bn2d_part_stats(_stream(), x.data_ptr(), ldx, x.shape[0], c, part.data_ptr()),
+               "nm_bn2d_part_stats")
+    return part
+
+
+def bn2d_merge(parts, batch_mean, batch_var, total, moving_mean=None, moving_var=None, momentum=BN_MOMENTUM):
+    """The statistics of all rows from ``parts`` (float64 [world, 2C + 1], in rank order) (nm_bn2d_merge): the mean, the
+    biased variance, ``total`` (float64 [1]: the row count) and, when given, the moving statistics' step."""
+    c = batch_mean.numel()
+    assert _f64(parts).is_contiguous() and parts.dim() == 2 and parts.shape[1] == bn2d_part_doubles(c)
+    assert _f64(total).numel() == 1
+    for t in (moving_mean, moving_var, batch_mean, batch_var):
+        assert t is None or (_f32(t).is_contiguous() and t.numel() == c)
+    _lib.check(_lib.load().nm_bn2d_merge(_stream(), parts.data_ptr(), parts.shape[0], c, float(momentum), _p(moving_mean),
+                                         _p(moving_var), batch_mean.data_ptr(), batch_var.data_ptr(), total.data_ptr()),
+               "nm_bn2d_merge")
+
+
+def bn2d_bwd_sums(x, y, dy, mean, var, relu, sums, dgamma=None, dbeta=None, accumulate_params=True, eps=BN_EPSILON):
+    """The first half of ``bn2d_bwd`` from the merged ``mean`` / ``var``: this rank's two channel sums into ``sums``
+    [2C], and into ``dgamma`` / ``dbeta`` (nm_bn2d_bwd_sums)."""
+    c = x.shape[1]
+    ldx, lddy = _ld2(x, c, "bn2d_bwd_sums x"), _ld2(dy, c, "bn2d_bwd_sums dy")
+    ldy = 0 if y is None else _ld2(y, c, "bn2d_bwd_sums y")
+    assert dy.shape == x.shape and (y is None or y.shape == x.shape)
+    assert _f32(sums).is_contiguous() and sums.numel() == 2 * c
+    for t in (mean, var, dgamma, dbeta):
+        assert t is None or (_f32(t).is_contiguous() and t.numel() == c)
+    _lib.check(_lib.load().nm_bn2d_bwd_sums(_stream(), x.data_ptr(), ldx, _p(y), ldy, dy.data_ptr(), lddy, x.shape[0], c,
+                                            mean.data_ptr(), var.data_ptr(), float(eps), int(bool(relu)),
+                                            sums.data_ptr(), _p(dgamma), _p(dbeta), int(bool(accumulate_params))),
+               "nm_bn2d_bwd_sums")
+
+
+def bn2d_bwd_dx(x, y, dy, gamma, mean, var, relu, sums, n, dx, accumulate_dx=False, eps=BN_EPSILON):
+    """The second half: dx from ``sums`` [2C] added over all ranks and the global row count ``n`` (nm_bn2d_bwd_dx)."""
+    c = x.shape[1]
+    ldx, lddy, lddx = _ld2(x, c, "bn2d_bwd_dx x"), _ld2(dy, c, "bn2d_bwd_dx dy"), _ld2(dx, c, "bn2d_bwd_dx dx")
+    ldy = 0 if y is None else _ld2(y, c, "bn2d_bwd_dx y")
+    assert dy.shape == x.shape and dx.shape == x.shape and (y is None or y.shape == x.shape)
+    assert _f32(sums).is_contiguous() and sums.numel() == 2 * c
+    for t in (gamma, mean, var):
+        assert _f32(t).is_contiguous() and t.numel() == c
+    _lib.check(_lib.load().nm_bn2d_bwd_dx(_stream(), x.data_ptr(), ldx, _p(y), ldy, dy.data_ptr(), lddy, x.shape[0], c,
+                                          gamma.data_ptr(), mean.data_ptr(), var.data_ptr(), float(eps),
+                                          int(bool(relu)), sums.data_ptr(), int(n), dx.data_ptr(), lddx,
+                                          int(bool(accumulate_dx))), "nm_bn2d_bwd_dx")
+
+
 def window2d_fwd(mode, x, y, window, stride, padding="valid", argmax=None):
     """y [B, OH, OW, C] = max / average of x [B, H, W, C] over ``window`` at ``stride`` (nm_window2d_fwd); ``argmax``
     (int32, the shape of y, contiguous): where the first maximum lies, for ``window2d_bwd``."""

@@ -161,7 +161,11 @@ class GenericTrainer(GraphExecutor, Feedable):
             # GLOBAL token count and gradients are summed over ranks
             count = dec.train_token_count(ctx)
             scale = ctx.buffer((id(self), "gscale", i), (1,))
-            if dp is not None:
+            if getattr(dec, "loss_is_batch_sum", False):
+                # a cost that is a plain sum over the sentences (CTCDecoder): every rank back-propagates the objective's
+                # weight, and the gradients summed over the ranks are the full-batch sum's -- no count, no collective
+                ops.fill(scale, weight)
+            elif dp is not None:
                 dp.scale_by_global_count(count, weight, scale)               # on the device: no host exchange
             else:
                 ops.fill(scale, weight / count if count else 0.0)               # a batch without target tokens: no gradient
