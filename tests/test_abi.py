@@ -145,6 +145,52 @@ def test_round6_entry_points_validate_before_any_launch(lib):
     assert rc < 0 and b"nm_attn_step_bwd: bad shape" in lib.nm_last_error()
 
 
+def test_sdp_attention_limits_are_refusals_before_any_launch(lib):
+    """Where the scaled dot-product entry points stop ("limits"): the key / value (and, backward, the
+    query / gradient) tiles of one head have to fit 160 KiB of LDS whichever kernel would run, and nm_sdp_attn_step
+    takes the decode kernel's head widths only.  Past the edge there is an error code and a text that names the
+    reason -- checked before anything is launched (no device here: a launch would fail differently).  Only the refused
+    side is called; the accepted side runs on the GPU (tests/test_sdp_variants_gpu.py).  The labelling aid of those
+    tests (tests/sdp_ref.py: variant) has to put the same edges in the same places."""
+    from . import sdp_ref as R
+    buf = (ctypes.c_float * 64)()
+
+    def bwd(tq, tk, dh, heads=2, rows=2):
+        d = heads * dh
+        return lib.nm_sdp_attn_bwd(None, buf, tq * d, buf, tk * d, buf, tk * d, None, 0, buf, buf, tq * d, rows, tq, tk,
+                                   heads, dh, 0, 1.0, 0, None, buf, tq * d, buf, tk * d, buf, tk * d, buf, 0)
+
+    def fwd(tq, tk, dh, heads=2, rows=2):
+        d = heads * dh
+        return lib.nm_sdp_attn_fwd(None, buf, tq * d, buf, tk * d, buf, tk * d, None, 0, rows, 1, tq, tk, heads, dh, 0,
+                                   1.0, 0, None, buf, tq * d, None)
+
+    # backward: 79 positions at dh = 128 need 164,636 bytes (78: 162,552); at dh = 64 the first refused count is 155
+    for tq, tk, dh in ((79, 79, 128), (160, 160, 64), (155, 155, 64), (200, 128, 64), (8, 302, 64)):
+        assert R.variant("bwd", tq, tk, 2, dh) == ("refused",)
+        assert bwd(tq, tk, dh) < 0, (tq, tk, dh)
+        msg = lib.nm_last_error()
+        assert b"nm_sdp_attn_bwd" in msg and b"do not fit LDS" in msg and ("Tq=%d Tk=%d dh=%d" % (tq, tk, dh)).encode() in msg
+    for tq, tk, dh in ((78, 78, 128), (154, 154, 64), (150, 150, 64)):
+        assert R.variant("bwd", tq, tk, 2, dh) != ("refused",)
+    # forward: the wave-per-query kernel's tiles, also where the decode or a matrix-core kernel would run
+    for tq, tk, dh in ((1, 310, 64), (1, 302, 64), (1, 154, 128), (64, 154, 128)):
+        assert R.variant("fwd", tq, tk, 2, dh) == ("refused",)
+        assert fwd(tq, tk, dh) < 0, (tq, tk, dh)
+        msg = lib.nm_last_error()
+        assert b"nm_sdp_attn_fwd" in msg and b"does not fit LDS" in msg and ("Tk=%d x dh=%d" % (tk, dh)).encode() in msg
+    for tq, tk, dh in ((1, 301, 64), (128, 128, 128), (1, 153, 128)):
+        assert R.variant("fwd", tq, tk, 2, dh) != ("refused",)
+    # one cached step: head widths the decode kernel has no instantiation for
+    anc = (ctypes.c_int32 * 64)()
+    for dh in (12, 2, 20, 192, 512):
+        assert R.variant("step", 1, 2, 2, dh) == ("refused",)
+        rc = lib.nm_sdp_attn_step(None, buf, 2 * dh, buf, 4 * dh, buf, 4 * dh, None, 0, 1, 2, 2, dh, anc, 2, buf, 2 * dh,
+                                  None)
+        assert rc < 0 and ("nm_sdp_attn_step: dh=%d must be" % dh).encode() in lib.nm_last_error()
+    assert all(R.variant("step", 1, 2, 2, dh) == ("decode", dh // 4) for dh in (4, 8, 16, 32, 64, 128, 256))
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from neuralmonkey_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
