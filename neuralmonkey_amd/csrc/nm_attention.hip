@@ -22,6 +22,7 @@
 // The softmax-then-mask-renorm of the reference is carried exactly:
 //   w_s = exp(e_s-M) m_s / (sum_j exp(e_j-M) m_j + 1e-8 * sum_j exp(e_j-M)).
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 #include <stdlib.h>
 #include <utility>

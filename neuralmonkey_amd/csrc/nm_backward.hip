@@ -6,6 +6,8 @@
 // projections, logits) is differentiated batched over all T steps; the
 // sequential part is two skinny NT GEMMs + the two epilogues below per step.
 #include "nm_common.h"
+#include "../../include/nmhip.h"
+#include "nm_gru.h"
 
 // ---------------------------------------------------------------------------
 // dpre = dy * (1 - y^2)  in place (tanh epilogue of the output projection)
@@ -649,16 +651,8 @@ struct GruBwdArgs {
 
 __device__ __forceinline__ bool gru_bwd_pos(const GruBwdArgs& a, int r, int d, int& pos, int& ppos,
                                             bool& first) {
-    pos = a.t;
-    const bool rev = (a.rev_mask >> d) & 1;
-    if (a.lengths) {
-        const int len = a.lengths[r];
-        if (a.t >= len) return false;
-        if (rev) pos = len - 1 - a.t;
-    }
-    ppos = rev ? pos + 1 : pos - 1;
     first = (a.t == 0);
-    return true;
+    return gru_step_pos(a.lengths, a.rev_mask, r, d, a.t, pos, ppos);
 }
 
 __device__ __forceinline__ float4 gru_hprev(const GruBwdArgs& a, long ro, int d, long r, int ppos,

@@ -17,6 +17,7 @@
 // therefore has no link-time dependency on RCCL, and a machine without it gets an error code from
 // nm_allreduce_init, not a load failure of the whole library.
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 #include <dlfcn.h>
 

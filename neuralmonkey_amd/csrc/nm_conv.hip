@@ -26,6 +26,7 @@
 //                     implicit GEMM with a GLU + residual epilogue in registers; its gradients reuse conv_mfma<true>
 //                     and the weight-gradient kernels through conv_grads_launch (further down).
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

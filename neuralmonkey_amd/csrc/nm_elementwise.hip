@@ -7,6 +7,7 @@
 //   encoders/recurrent.py:86-102         dynamic_rnn length masking + reverse_sequence
 //   tf_utils.py:189-219                  layer_norm
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 thread_local char nm_err_buf[512] = {0};
 extern "C" const char* nm_last_error(void) { return nm_err_buf; }

@@ -10,6 +10,7 @@
 //   nm_reverse_sequence tf.reverse_sequence by lengths       (bidirectional_dynamic_rnn)
 //   nm_maxout_fwd/bwd   max-pool of a dense output           (nn/projection.py:7-35)
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 // ---------------------------------------------------------------------------------------------
 // op codes of nm_ew (mirrored in neuralmonkey_amd/ops.py)

@@ -16,6 +16,7 @@
 // ds_read_b128 sweep).  The kernel exists to put a NUMBER on the emulation (tools/gemm_bf16x3_cost.py,
 // bench.py `configs.logits_gemm_bf16x3`); the shipped path stays exact fp32.
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 #include <mutex>
 

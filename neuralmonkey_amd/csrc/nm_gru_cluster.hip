@@ -43,6 +43,7 @@
 #include <stdlib.h>
 
 #include "nm_gru.h"
+#include "../../include/nmhip_gru_seq.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1284,11 +1285,40 @@ extern "C" int nm_gru_seq_supported(int64_t R, int64_t H, int32_t ndir) {
     return clu_shape(R, H, ndir, &s) ? 1 : 0;
 }
 
-// header + granules: forward two stage outputs of width H, backward one of width H and two copies of width 2H
-extern "C" int64_t nm_gru_seq_workspace_bytes(int64_t R, int64_t H, int32_t ndir) {
+// What a loop takes of its workspace and of LDS, written ONCE: the *_workspace_bytes functions and the launchers both
+// read it (a buffer that is too small or not cleared is a give-up or wrong numbers, never a compile error).  A buffer is
+// the granules of one stage output of width H, all clusters (CluShape::granules of 8 bytes), behind the header.
+struct CluLayout {
+    int bufs;                    // buffers in the workspace; xa is the first
+    int xb;                      // xb starts this many buffers behind xa
+    int cleared[2];              // buffers zeroed (with the header) in front of a forward / backward launch
+    int lds_kib[2];              // LDS per wave and row tile, forward / backward
+};
+// GRU: forward two stage outputs of width H, backward one of width H and two copies of width 2H
+static constexpr CluLayout CLU_GRU = {5, 1, {2, 5}, {3, 2}};
+// NematusGRU: two buffers of width 3H (the backward loop's; the forward loop uses the first H columns' worth)
+static constexpr CluLayout CLU_NEMATUS = {6, 3, {6, 6}, {3, 1}};
+// LSTM: two buffers of width 4H (the backward loop's; the forward loop's two of width H fit inside)
+static constexpr CluLayout CLU_LSTM = {8, 4, {8, 8}, {4, 1}};
+
+static int64_t clu_workspace_bytes(const CluLayout& lay, const CluShape& s) {
+    return CLU_HDR_BYTES + s.granules * 8 * lay.bufs;
+}
+
+// (a shape the kernels do not take: the bare header)
+static int64_t clu_workspace_bytes(const CluLayout& lay, int64_t R, int64_t H, int32_t ndir) {
     CluShape s;
-    if (!clu_shape(R, H, ndir, &s)) return CLU_HDR_BYTES;
-    return CLU_HDR_BYTES + s.granules * 8 * 5;
+    return clu_shape(R, H, ndir, &s) ? clu_workspace_bytes(lay, s) : CLU_HDR_BYTES;
+}
+
+extern "C" int64_t nm_gru_seq_workspace_bytes(int64_t R, int64_t H, int32_t ndir) {
+    return clu_workspace_bytes(CLU_GRU, R, H, ndir);
+}
+extern "C" int64_t nm_nematus_seq_workspace_bytes(int64_t R, int64_t H, int32_t ndir) {
+    return clu_workspace_bytes(CLU_NEMATUS, R, H, ndir);
+}
+extern "C" int64_t nm_lstm_seq_workspace_bytes(int64_t R, int64_t H, int32_t ndir) {
+    return clu_workspace_bytes(CLU_LSTM, R, H, ndir);
 }
 
 template <typename Kern>
@@ -1356,6 +1386,17 @@ extern "C" int nm_test_xcc_ids(void* stream, int32_t* xcc_out, int32_t blocks, i
     NM_LAUNCH_CHECK("nm_test_xcc_ids");
 }
 
+// Test hooks every cluster launch reads (the loops and the decoder step): NM_CLUSTER_PLACEMENT=blockidx takes the
+// placement-independent path (what runs when an XCD does not get its tickets), and the next
+// nm_gru_seq_force_give_up(n) launches behave like launches whose hand-offs timed out.
+static void clu_test_hooks(int* force_global, int* force_fail) {
+    const char* place = getenv("NM_CLUSTER_PLACEMENT");
+    *force_global = (place && strcmp(place, "blockidx") == 0) ? 1 : 0;
+    int left = clu_force_fail.load(std::memory_order_relaxed);
+    while (left > 0 && !clu_force_fail.compare_exchange_weak(left, left - 1, std::memory_order_relaxed)) { }
+    *force_fail = left > 0 ? 1 : 0;
+}
+
 static void clu_fill(GruClu& q, const nm_gru_epilogue* e) {
     GruEpi& d = q.e;
     d.mode = 0; d.lengths = e->lengths; d.t = 0; d.rev_mask = e->rev_mask; d.H = (int)e->H; d.R = e->R;
@@ -1368,42 +1409,64 @@ static void clu_fill(GruClu& q, const nm_gru_epilogue* e) {
     d.dgpre = e->dgpre; d.dcpre = e->dcpre;
     q.ndir = e->ndir;
     clu_no_io(q);
-    {   // test hook: the placement-independent path (what runs when an XCD does not get its tickets)
-        const char* place = getenv("NM_CLUSTER_PLACEMENT");
-        q.force_global = (place && strcmp(place, "blockidx") == 0) ? 1 : 0;
-    }
+    clu_test_hooks(&q.force_global, &q.force_fail);
     q.dbg = nullptr;
-    {   // test hook: the next nm_gru_seq_force_give_up(n) launches behave like launches whose hand-offs timed out
-        int left = clu_force_fail.load(std::memory_order_relaxed);
-        q.force_fail = 0;
-        while (left > 0 && !clu_force_fail.compare_exchange_weak(left, left - 1, std::memory_order_relaxed)) { }
-        if (left > 0) q.force_fail = 1;
-    }
 #ifdef NM_CLU_DEBUG          // timing probe of one workgroup (tools/clu_stamps.py): a device buffer of 64 longs
     if (getenv("NM_CLU_DEBUG_PTR")) q.dbg = reinterpret_cast<long*>(strtoull(getenv("NM_CLU_DEBUG_PTR"), nullptr, 0));
 #endif
 }
 
-// mirrors include/nmhip_gru_seq.h: what the callers of the plain entry points launch around a loop, done by the loop
-struct nm_gru_seq_io {
-    int32_t zero_padded, reserved;
-    float* final_state; int64_t final_row, final_dir;
-    float* hprev_seq; float* rh_seq; int64_t seq_dir, seq_row, seq_time;
-    float* h0_out;
-    const float* d_final; int64_t dfinal_row, dfinal_dir;
-};
+// The front of every loop's launcher.  The checks all loops make, in the order all loops make them: pointers, shape,
+// then ``own()`` -- the loop's operand, alignment and io rules, which return NM_OK or refuse like NM_REQUIRE -- then what
+// the device takes and the size of the workspace.  When there is something to launch, ``q`` gets everything that does
+// not depend on the cell type: the epilogue's operands, the hooks, steps / nrb / hdr / sticky and the two granule
+// pointers.  Returns < 0 after a refusal, 0 when there is nothing to do (steps == 0) and 1 to go on.
+template <typename Own>
+static int clu_begin(const char* who, const CluLayout& lay, const nm_gru_epilogue* e, bool kernels, int32_t steps,
+                     void* workspace, int64_t workspace_bytes, uint32_t* sticky_error, Own own, GruClu& q, CluShape& s) {
+    NM_REQUIRE(e && kernels && workspace, "%s: null pointer / workspace", who);
+    NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2,
+               "%s: bad shape R=%ld H=%ld", who, (long)e->R, (long)e->H);
+    const int rc = own();
+    if (rc != NM_OK) return rc;
+    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported "
+               "(nm_gru_seq_supported)", who, (long)e->R, (long)e->H, (int)e->ndir);
+    NM_REQUIRE(workspace_bytes >= clu_workspace_bytes(lay, s), "%s: workspace too small", who);
+    if (steps == 0) return 0;
+    clu_fill(q, e);
+    q.steps = steps; q.nrb = s.nrb;
+    q.hdr = reinterpret_cast<unsigned*>(workspace);
+    q.sticky = sticky_error;
+    q.xa = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + CLU_HDR_BYTES);
+    q.xb = q.xa + s.granules * lay.xb;
+    return 1;
+}
+
+// The back of every loop's launcher: header and granules zeroed, then the loop's kernel for the shape's row tiles
+// (``rt1`` / ``rt2``: its instantiations for 16 / 32 rows per cluster) with ``arg``, whose hdr is ``workspace``.
+template <typename Arg>
+static int clu_launch(const char* who, const CluLayout& lay, bool backward, const CluShape& s, void* stream,
+                      void* workspace, void (*rt1)(Arg), void (*rt2)(Arg), const Arg& arg) {
+    hipStream_t st = nm_stream(stream);
+    if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * lay.cleared[backward], st) != hipSuccess)
+        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
+    const size_t lds = (size_t)s.NW * s.RT * lay.lds_kib[backward] * 1024;
+    void (*kern)(Arg) = s.RT == 1 ? rt1 : rt2;
+    if (!clu_prepare(kern, lds)) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
+    hipLaunchKernelGGL(kern, dim3(s.grid), dim3(s.NW * 64), lds, st, arg);
+    NM_LAUNCH_CHECK(who);
+}
 
 // io == null: the plain entry point (h_in required, nothing fused)
 static int gru_seq_fwd_launch(const char* who, void* stream, const nm_gru_epilogue* e, const nm_gru_seq_io* io,
                               int32_t steps, int64_t h_step, int64_t ru_step, int64_t rh_step, int64_t c_step,
                               const float* wgh, int64_t ld_g, int64_t stride_g, const float* wch, int64_t ld_c,
                               int64_t stride_c, void* workspace, int64_t workspace_bytes, uint32_t* sticky_error) {
-    NM_REQUIRE(e && wgh && wch && workspace, "%s: null pointer / workspace", who);
-    NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2,
-               "%s: bad shape R=%ld H=%ld", who, (long)e->R, (long)e->H);
-    NM_REQUIRE(e->xp && (e->h_in || io) && e->h_out && e->ru, "%s: missing operand", who);
-    NM_REQUIRE(nm_aligned16(e->h_in) && nm_aligned16(workspace), "%s: operands must be 16-byte aligned", who);
-    if (io) {
+    const auto own = [&]() -> int {
+        NM_REQUIRE(e->xp && (e->h_in || io) && e->h_out && e->ru, "%s: missing operand", who);
+        // (h_in and the workspace only: this loop never asked for aligned kernels)
+        NM_REQUIRE(nm_aligned16(e->h_in) && nm_aligned16(workspace), "%s: operands must be 16-byte aligned", who);
+        if (!io) return NM_OK;
         const int64_t H = e->H;
         const bool two = e->ndir == 2;
         NM_REQUIRE(!io->final_state || (io->final_row >= H && io->final_dir >= 0 && (!two || io->final_dir >= H)),
@@ -1415,14 +1478,12 @@ static int gru_seq_fwd_launch(const char* who, void* stream, const nm_gru_epilog
                    (long)io->seq_dir, (long)io->seq_row, (long)io->seq_time, (long)H);
         NM_REQUIRE(!io->zero_padded || e->out, "%s: zero_padded without out", who);
         NM_REQUIRE(!io->h0_out || (io->h0_out != e->h_in && io->h0_out != e->h_out), "%s: h0_out may not alias h_in / h_out", who);
-    }
-    CluShape s;
-    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported "
-               "(nm_gru_seq_supported)", who, (long)e->R, (long)e->H, (int)e->ndir);
-    NM_REQUIRE(workspace_bytes >= nm_gru_seq_workspace_bytes(e->R, e->H, e->ndir), "%s: workspace too small", who);
-    if (steps == 0) return NM_OK;
+        return NM_OK;
+    };
     GruClu q;
-    clu_fill(q, e);
+    CluShape s;
+    const int go = clu_begin(who, CLU_GRU, e, wgh && wch, steps, workspace, workspace_bytes, sticky_error, own, q, s);
+    if (go <= 0) return go;
     if (io) {
         q.zero_padded = io->zero_padded ? 1 : 0;
         q.fin = io->final_state; q.fin_row = io->final_row; q.fin_dir = io->final_dir;
@@ -1430,27 +1491,9 @@ static int gru_seq_fwd_launch(const char* who, void* stream, const nm_gru_epilog
         q.sq_dir = io->seq_dir; q.sq_row = io->seq_row; q.sq_time = io->seq_time;
         q.h0_out = io->h0_out;
     }
-    q.steps = steps; q.nrb = s.nrb;
     q.h_step = h_step; q.ru_step = ru_step; q.rh_step = rh_step; q.c_step = c_step;
     q.wg = wgh; q.ldg = ld_g; q.sg = stride_g; q.wc = wch; q.ldc = ld_c; q.sc = stride_c;
-    q.hdr = reinterpret_cast<unsigned*>(workspace);
-    q.sticky = sticky_error;
-    q.xa = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + CLU_HDR_BYTES);
-    q.xb = q.xa + s.granules;
-    hipStream_t st = nm_stream(stream);
-    if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * 2, st) != hipSuccess)
-        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
-    const size_t lds = (size_t)s.NW * s.RT * 3 * 1024;
-    bool ok;
-    if (s.RT == 1) {
-        ok = clu_prepare(gru_cluster_fwd_kernel<1>, lds);
-        if (ok) hipLaunchKernelGGL((gru_cluster_fwd_kernel<1>), dim3(s.grid), dim3(s.NW * 64), lds, st, q);
-    } else {
-        ok = clu_prepare(gru_cluster_fwd_kernel<2>, lds);
-        if (ok) hipLaunchKernelGGL((gru_cluster_fwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, q);
-    }
-    if (!ok) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
-    NM_LAUNCH_CHECK(who);
+    return clu_launch(who, CLU_GRU, false, s, stream, workspace, gru_cluster_fwd_kernel<1>, gru_cluster_fwd_kernel<2>, q);
 }
 
 extern "C" int nm_gru_seq_fwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t h_step,
@@ -1481,52 +1524,29 @@ static int gru_seq_bwd_launch(const char* who, void* stream, const nm_gru_epilog
                               int32_t steps, int64_t ru_step, int64_t c_step, const float* wgh, int64_t ld_g,
                               int64_t stride_g, const float* wch, int64_t ld_c, int64_t stride_c, void* workspace,
                               int64_t workspace_bytes, uint32_t* sticky_error) {
-    NM_REQUIRE(e && wgh && wch && workspace, "%s: null pointer / workspace", who);
-    NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2,
-               "%s: bad shape R=%ld H=%ld", who, (long)e->R, (long)e->H);
-    NM_REQUIRE(e->dh && e->ru && e->c && e->hseq && e->dxp, "%s: missing operand", who);
-    NM_REQUIRE(nm_aligned16(wgh) && nm_aligned16(wch) && ld_g % 4 == 0 && ld_c % 4 == 0 && stride_g % 4 == 0 &&
-                   stride_c % 4 == 0 && nm_aligned16(workspace),
-               "%s: kernels must be 16-byte aligned with leading dimensions %% 4 == 0", who);
-    if (io) {
+    const auto own = [&]() -> int {
+        NM_REQUIRE(e->dh && e->ru && e->c && e->hseq && e->dxp, "%s: missing operand", who);
+        NM_REQUIRE(nm_aligned16(wgh) && nm_aligned16(wch) && ld_g % 4 == 0 && ld_c % 4 == 0 && stride_g % 4 == 0 &&
+                       stride_c % 4 == 0 && nm_aligned16(workspace),
+                   "%s: kernels must be 16-byte aligned with leading dimensions %% 4 == 0", who);
         const bool two = e->ndir == 2;
-        NM_REQUIRE(!io->d_final || (io->dfinal_row >= e->H && io->dfinal_dir >= 0 && (!two || io->dfinal_dir >= e->H)),
+        NM_REQUIRE(!io || !io->d_final || (io->dfinal_row >= e->H && io->dfinal_dir >= 0 && (!two || io->dfinal_dir >= e->H)),
                    "%s: inconsistent strides of d_final (row %ld, direction %ld, H %ld)", who, (long)io->dfinal_row,
                    (long)io->dfinal_dir, (long)e->H);
-    }
-    CluShape s;
-    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported "
-               "(nm_gru_seq_supported)", who, (long)e->R, (long)e->H, (int)e->ndir);
-    NM_REQUIRE(workspace_bytes >= nm_gru_seq_workspace_bytes(e->R, e->H, e->ndir), "%s: workspace too small", who);
-    if (steps == 0) return NM_OK;
+        return NM_OK;
+    };
     GruClu q;
-    clu_fill(q, e);
+    CluShape s;
+    const int go = clu_begin(who, CLU_GRU, e, wgh && wch, steps, workspace, workspace_bytes, sticky_error, own, q, s);
+    if (go <= 0) return go;
     if (io) {
         q.zero_padded = io->zero_padded ? 1 : 0;
         q.dfin = io->d_final; q.dfin_row = io->dfinal_row; q.dfin_dir = io->dfinal_dir;
         q.dh_from_dfin = 1;
     }
-    q.steps = steps; q.nrb = s.nrb;
     q.h_step = 0; q.ru_step = ru_step; q.rh_step = 0; q.c_step = c_step;
     q.wg = wgh; q.ldg = ld_g; q.sg = stride_g; q.wc = wch; q.ldc = ld_c; q.sc = stride_c;
-    q.hdr = reinterpret_cast<unsigned*>(workspace);
-    q.sticky = sticky_error;
-    q.xa = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + CLU_HDR_BYTES);
-    q.xb = q.xa + s.granules;
-    hipStream_t st = nm_stream(stream);
-    if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * 5, st) != hipSuccess)
-        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
-    const size_t lds = (size_t)s.NW * s.RT * 2 * 1024;
-    bool ok;
-    if (s.RT == 1) {
-        ok = clu_prepare(gru_cluster_bwd_kernel<1>, lds);
-        if (ok) hipLaunchKernelGGL((gru_cluster_bwd_kernel<1>), dim3(s.grid), dim3(s.NW * 64), lds, st, q);
-    } else {
-        ok = clu_prepare(gru_cluster_bwd_kernel<2>, lds);
-        if (ok) hipLaunchKernelGGL((gru_cluster_bwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, q);
-    }
-    if (!ok) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
-    NM_LAUNCH_CHECK(who);
+    return clu_launch(who, CLU_GRU, true, s, stream, workspace, gru_cluster_bwd_kernel<1>, gru_cluster_bwd_kernel<2>, q);
 }
 
 extern "C" int nm_gru_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t ru_step, int64_t c_step,
@@ -1609,73 +1629,39 @@ bool nm_dec_step_cluster_try(hipStream_t st, int64_t R, int64_t H, int64_t A, in
     q.xa = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + CLU_HDR_BYTES);
     q.xb = q.xa + (long)ncl * 16 * H;
     q.sticky = sticky;
-    {
-        const char* place = getenv("NM_CLUSTER_PLACEMENT");
-        q.force_global = (place && strcmp(place, "blockidx") == 0) ? 1 : 0;
-        int left = clu_force_fail.load(std::memory_order_relaxed);
-        q.force_fail = 0;
-        while (left > 0 && !clu_force_fail.compare_exchange_weak(left, left - 1, std::memory_order_relaxed)) { }
-        if (left > 0) q.force_fail = 1;
-    }
+    clu_test_hooks(&q.force_global, &q.force_fail);
     hipLaunchKernelGGL(dec_step_cluster_kernel, dim3(grid), dim3(nw * 64), lds, st, q);
     return hipGetLastError() == hipSuccess;
 }
 
 // ---- NematusGRU loops: host side ------------------------------------------------------------------------------------
-// workspace: header + two buffers of width 3H (the backward loop's; the forward loop uses the first H columns' worth)
-extern "C" int64_t nm_nematus_seq_workspace_bytes(int64_t R, int64_t H, int32_t ndir) {
-    CluShape s;
-    if (!clu_shape(R, H, ndir, &s)) return CLU_HDR_BYTES;
-    return CLU_HDR_BYTES + s.granules * 8 * 6;
-}
-
 static int nem_launch(bool backward, void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t h_step, int64_t ru_step,
                       int64_t sc_step, int64_t c_step, const float* ug, int64_t ld_g, int64_t stride_g, const float* uc,
                       int64_t ld_c, int64_t stride_c, const float* bgs, const float* bcs, void* workspace,
                       int64_t workspace_bytes, uint32_t* sticky_error, const char* who) {
-    NM_REQUIRE(e && ug && uc && workspace, "%s: null pointer / workspace", who);
-    NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2, "%s: bad shape R=%ld H=%ld", who,
-               (long)e->R, (long)e->H);
-    NM_REQUIRE(nm_aligned16(workspace) && nm_aligned16(ug) && nm_aligned16(uc) && ld_g % 4 == 0 && ld_c % 4 == 0 &&
-                   stride_g % 4 == 0 && stride_c % 4 == 0, "%s: kernels / workspace must be 16-byte aligned", who);
-    if (backward) NM_REQUIRE(e->dh && e->ru && e->c && e->rh && e->hseq && e->dxp, "%s: missing operand", who);
-    else {
-        NM_REQUIRE(e->xp && e->h_in && e->h_out && e->ru && e->c_save && e->rh && nm_aligned16(e->h_in),
-                   "%s: missing / unaligned operand", who);
-        // (a step here is ONE stage: a workgroup may finish step 0 -- and write h_out -- while another still loads h_in)
-        NM_REQUIRE(e->h_in != e->h_out, "%s: h_in and h_out must be different buffers", who);
-    }
-    CluShape s;
-    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported (nm_gru_seq_supported)",
-               who, (long)e->R, (long)e->H, (int)e->ndir);
-    NM_REQUIRE(workspace_bytes >= nm_nematus_seq_workspace_bytes(e->R, e->H, e->ndir), "%s: workspace too small", who);
-    if (steps == 0) return NM_OK;
+    const auto own = [&]() -> int {
+        NM_REQUIRE(nm_aligned16(workspace) && nm_aligned16(ug) && nm_aligned16(uc) && ld_g % 4 == 0 && ld_c % 4 == 0 &&
+                       stride_g % 4 == 0 && stride_c % 4 == 0, "%s: kernels / workspace must be 16-byte aligned", who);
+        if (backward) NM_REQUIRE(e->dh && e->ru && e->c && e->rh && e->hseq && e->dxp, "%s: missing operand", who);
+        else {
+            NM_REQUIRE(e->xp && e->h_in && e->h_out && e->ru && e->c_save && e->rh && nm_aligned16(e->h_in),
+                       "%s: missing / unaligned operand", who);
+            // (a step here is ONE stage: a workgroup may finish step 0 -- and write h_out -- while another still loads h_in)
+            NM_REQUIRE(e->h_in != e->h_out, "%s: h_in and h_out must be different buffers", who);
+        }
+        return NM_OK;
+    };
     NemClu a;
     GruClu& q = a.q;
-    clu_fill(q, e);
-    q.e.rh = e->rh;
-    q.steps = steps; q.nrb = s.nrb;
+    CluShape s;
+    const int go = clu_begin(who, CLU_NEMATUS, e, ug && uc, steps, workspace, workspace_bytes, sticky_error, own, q, s);
+    if (go <= 0) return go;
     q.h_step = h_step; q.ru_step = ru_step; q.rh_step = sc_step; q.c_step = c_step;
     q.wg = ug; q.ldg = ld_g; q.sg = stride_g; q.wc = uc; q.ldc = ld_c; q.sc = stride_c;
-    q.hdr = reinterpret_cast<unsigned*>(workspace);
-    q.sticky = sticky_error;
-    q.xa = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + CLU_HDR_BYTES);
-    q.xb = q.xa + s.granules * 3;
     a.bgs = bgs; a.bcs = bcs;
-    hipStream_t st = nm_stream(stream);
-    if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * 6, st) != hipSuccess)
-        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
-    const size_t lds = (size_t)s.NW * s.RT * (backward ? 1 : 3) * 1024;
-    bool ok;
-    if (backward) {
-        if (s.RT == 1) { ok = clu_prepare(nematus_cluster_bwd_kernel<1>, lds); if (ok) hipLaunchKernelGGL((nematus_cluster_bwd_kernel<1>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-        else { ok = clu_prepare(nematus_cluster_bwd_kernel<2>, lds); if (ok) hipLaunchKernelGGL((nematus_cluster_bwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-    } else {
-        if (s.RT == 1) { ok = clu_prepare(nematus_cluster_fwd_kernel<1>, lds); if (ok) hipLaunchKernelGGL((nematus_cluster_fwd_kernel<1>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-        else { ok = clu_prepare(nematus_cluster_fwd_kernel<2>, lds); if (ok) hipLaunchKernelGGL((nematus_cluster_fwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-    }
-    if (!ok) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
-    NM_LAUNCH_CHECK(who);
+    if (backward)
+        return clu_launch(who, CLU_NEMATUS, true, s, stream, workspace, nematus_cluster_bwd_kernel<1>, nematus_cluster_bwd_kernel<2>, a);
+    return clu_launch(who, CLU_NEMATUS, false, s, stream, workspace, nematus_cluster_fwd_kernel<1>, nematus_cluster_fwd_kernel<2>, a);
 }
 
 // e->rh: sc of every step ([steps] x sc_step); ug [ndir][H][2H], uc [ndir][H][H]: the STATE projections; bgs / bcs: their
@@ -1699,57 +1685,31 @@ extern "C" int nm_nematus_seq_bwd(void* stream, const nm_gru_epilogue* e, int32_
 }
 
 // ---- LSTM loops: host side ------------------------------------------------------------------------------------------
-// workspace: header + two buffers of width 4H (the backward loop's; the forward loop's two of width H fit inside)
-extern "C" int64_t nm_lstm_seq_workspace_bytes(int64_t R, int64_t H, int32_t ndir) {
-    CluShape s;
-    if (!clu_shape(R, H, ndir, &s)) return CLU_HDR_BYTES;
-    return CLU_HDR_BYTES + s.granules * 8 * 8;
-}
-
 static int lstm_launch(bool backward, void* stream, const nm_gru_epilogue* e, int32_t steps, int64_t h_step, int64_t g_step,
                        int64_t c_step, const float* wh, int64_t ld_w, int64_t stride_w, float forget_bias, void* workspace,
                        int64_t workspace_bytes, uint32_t* sticky_error, const char* who) {
-    NM_REQUIRE(e && wh && workspace, "%s: null pointer / workspace", who);
-    NM_REQUIRE(steps >= 0 && e->R > 0 && e->H > 0 && e->ndir >= 1 && e->ndir <= 2, "%s: bad shape R=%ld H=%ld", who,
-               (long)e->R, (long)e->H);
-    NM_REQUIRE(nm_aligned16(workspace) && nm_aligned16(wh) && ld_w % 4 == 0 && stride_w % 4 == 0,
-               "%s: kernel / workspace must be 16-byte aligned", who);
-    if (backward) NM_REQUIRE(e->dh && e->ru && e->c && e->dxp, "%s: missing operand", who);
-    else {
-        NM_REQUIRE(e->xp && e->h_in && e->h_out && e->ru && e->c_save && nm_aligned16(e->h_in),
-                   "%s: missing / unaligned operand", who);
-        NM_REQUIRE(e->h_in != e->h_out, "%s: h_in and h_out must be different buffers", who);
-    }
-    CluShape s;
-    NM_REQUIRE(clu_shape(e->R, e->H, e->ndir, &s), "%s: shape R=%ld H=%ld ndir=%d not supported (nm_gru_seq_supported)",
-               who, (long)e->R, (long)e->H, (int)e->ndir);
-    NM_REQUIRE(workspace_bytes >= nm_lstm_seq_workspace_bytes(e->R, e->H, e->ndir), "%s: workspace too small", who);
-    if (steps == 0) return NM_OK;
+    const auto own = [&]() -> int {
+        NM_REQUIRE(nm_aligned16(workspace) && nm_aligned16(wh) && ld_w % 4 == 0 && stride_w % 4 == 0,
+                   "%s: kernel / workspace must be 16-byte aligned", who);
+        if (backward) NM_REQUIRE(e->dh && e->ru && e->c && e->dxp, "%s: missing operand", who);
+        else {
+            NM_REQUIRE(e->xp && e->h_in && e->h_out && e->ru && e->c_save && nm_aligned16(e->h_in),
+                       "%s: missing / unaligned operand", who);
+            NM_REQUIRE(e->h_in != e->h_out, "%s: h_in and h_out must be different buffers", who);
+        }
+        return NM_OK;
+    };
     LstmClu a;
     GruClu& q = a.q;
-    clu_fill(q, e);
-    q.steps = steps; q.nrb = s.nrb;
+    CluShape s;
+    const int go = clu_begin(who, CLU_LSTM, e, wh != nullptr, steps, workspace, workspace_bytes, sticky_error, own, q, s);
+    if (go <= 0) return go;
     q.h_step = h_step; q.ru_step = g_step; q.rh_step = 0; q.c_step = c_step;
     q.wg = wh; q.ldg = ld_w; q.sg = stride_w; q.wc = nullptr; q.ldc = 0; q.sc = 0;
-    q.hdr = reinterpret_cast<unsigned*>(workspace);
-    q.sticky = sticky_error;
-    q.xa = reinterpret_cast<u64*>(reinterpret_cast<char*>(workspace) + CLU_HDR_BYTES);
-    q.xb = q.xa + s.granules * 4;
     a.forget_bias = forget_bias;
-    hipStream_t st = nm_stream(stream);
-    if (hipMemsetAsync(workspace, 0, CLU_HDR_BYTES + (size_t)s.granules * 8 * 8, st) != hipSuccess)
-        NM_FAIL(NM_ERR_HIP, "%s: memset failed", who);
-    const size_t lds = (size_t)s.NW * s.RT * (backward ? 1 : 4) * 1024;
-    bool ok;
-    if (backward) {
-        if (s.RT == 1) { ok = clu_prepare(lstm_cluster_bwd_kernel<1>, lds); if (ok) hipLaunchKernelGGL((lstm_cluster_bwd_kernel<1>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-        else { ok = clu_prepare(lstm_cluster_bwd_kernel<2>, lds); if (ok) hipLaunchKernelGGL((lstm_cluster_bwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-    } else {
-        if (s.RT == 1) { ok = clu_prepare(lstm_cluster_fwd_kernel<1>, lds); if (ok) hipLaunchKernelGGL((lstm_cluster_fwd_kernel<1>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-        else { ok = clu_prepare(lstm_cluster_fwd_kernel<2>, lds); if (ok) hipLaunchKernelGGL((lstm_cluster_fwd_kernel<2>), dim3(s.grid), dim3(s.NW * 64), lds, st, a); }
-    }
-    if (!ok) NM_FAIL(NM_ERR_HIP, "%s: the kernel cannot be made resident on this device", who);
-    NM_LAUNCH_CHECK(who);
+    if (backward)
+        return clu_launch(who, CLU_LSTM, true, s, stream, workspace, lstm_cluster_bwd_kernel<1>, lstm_cluster_bwd_kernel<2>, a);
+    return clu_launch(who, CLU_LSTM, false, s, stream, workspace, lstm_cluster_fwd_kernel<1>, lstm_cluster_fwd_kernel<2>, a);
 }
 
 // e->ru: the activated gates [i | j | f | o] of every step ([steps] x g_step, 4H wide); e->c_save: c' of every step; xp 4H

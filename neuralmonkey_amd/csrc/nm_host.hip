@@ -6,6 +6,7 @@
 //               checkpoints carry per tensor and per index block (checkpoint import / export,
 //               neuralmonkey/tf_manager.py:274-288 -> tf.train.Saver).  Slicing-by-8, ~1 GB/s.
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 #include <mutex>
 #include <stdlib.h>

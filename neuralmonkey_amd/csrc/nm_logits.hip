@@ -6,6 +6,7 @@
 //   decoders/beam_search_decoder.py:440-501 masking, +logprob_sum, length penalty,
 //                                           tf.nn.top_k over [B, k*V], div/mod, gathers
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 #include <stdlib.h>
 
 #define NM_NEG_INF_F (-1e9f)   // the reference's INF (beam_search_decoder.py:42)

@@ -9,6 +9,7 @@
 // table maps fixed-size chunks to variables ("segments") so that three launches
 // cover every tensor and all reductions have a fixed order (deterministic).
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 struct OptChunks {
     const long* chunk_start;   // [nchunk] flat offset

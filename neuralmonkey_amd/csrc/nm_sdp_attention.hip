@@ -18,6 +18,7 @@
 // energy gradients and dQ, phase 2 (wave per key) reduces dK and dV over the queries -- no atomics,
 // deterministic.
 #include "nm_sdp.h"
+#include "../../include/nmhip.h"
 
 __global__ __launch_bounds__(256) void sdp_fwd_kernel(SdpArgs p) {
     extern __shared__ float sm[];

@@ -20,6 +20,7 @@
 // both fragments of a wave are single 16-byte loads and all loads of a wave are in flight before its first
 // MFMA.  Several products that do not depend on each other share one launch (a "group").
 #include "nm_common.h"
+#include "../../include/nmhip.h"
 
 #include <atomic>
 #include <stdlib.h>
@@ -544,22 +545,6 @@ static bool sgd_prepare() {
     return (seen & ok_bit) != 0;
 }
 
-struct nm_step_problem {          // mirrors include/nmhip.h
-    const float* A; int64_t lda;
-    const float* Bt; int64_t ldb;
-    int64_t N, K;
-    int32_t a_kind, epilogue, act, nchunk;
-    const float* bias; const float* add; int64_t ldadd;
-    float* C; int64_t ldc;
-    const float* pctx; const float* pstat;
-    const float* energies; const float* mask; float* weights; int64_t S, mask_div, mask_mod;
-    const float* h; int64_t ldh;
-    float* ru; float* rh;
-    const float* xc; int64_t ldxc;
-    float* h_out; int64_t ldho; float* h_out2; int64_t ldho2;
-    const int32_t* add_ids; const int32_t* xc_ids;
-};
-
 // OPT-IN (NM_STEP_DMA=1).  Measured per group of a 640-row step, alone and warm (tools/step_group_probe.py,
 // profiles/r06_step_group_probe.txt): 16.7 / 16.0 / 18.0 / 25.5 us against the register-staged kernels' 15.9 / 10.5 /
 // 19.1 / 16.5, and 26.7 us per group inside a beam step with one chunk in flight (profiles/
@@ -708,39 +693,6 @@ bool nm_medium_gemm(hipStream_t st, int transB, long M, long N, long K, const fl
 // attention, nonlinear output projection) followed by the vocabulary projection of get_body
 // (decoders/autoregressive.py:450-459).  Host sequencing only -- the seven launches are the ones documented at
 // the top of this file; a caller that replays the step (HIP graph) captures this call.
-extern "C" int nm_attn_fwd(void* stream, const float* y, const float* hf, const float* states, const float* mask,
-                           const float* v, const float* bias, int64_t R, int64_t rows_per_key, int64_t S, int64_t A,
-                           int64_t C, float* ctx, int64_t ldctx, float* weights, void* workspace,
-                           int64_t workspace_bytes, float* energies_out);
-extern "C" int nm_logits_stats_gemm(void* stream, int transB, int64_t M, int64_t N, int64_t K, const float* A,
-                                    int64_t lda, const float* B, int64_t ldb, const float* bias, float* C, int64_t ldc,
-                                    float* stats, int64_t stats_bytes);
-extern "C" int nm_gemm_f32(void* stream, int transA, int transB, int64_t M, int64_t N, int64_t K, const float* A,
-                           int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int act,
-                           int accumulate, int64_t batch, int64_t strideA, int64_t strideB, int64_t strideC, int algo,
-                           void* workspace, int64_t workspace_bytes);
-
-struct nm_decoder_step {          // mirrors include/nmhip.h
-    int64_t rows, emb, rnn, attn_state, ctx_width, out, vocab, src_len, rows_per_key;
-    float* cat;
-    float* h_copy; int64_t ld_h_copy;
-    float* out_state; int64_t ld_out_state;
-    float* attn_weights;
-    float* logits; int64_t ld_logits;
-    float* stats; int64_t stats_bytes;
-    float* ru; float* rh; float* xc; float* y; float* pre_e; float* pre; float* ctx;
-    void* attn_workspace; int64_t attn_workspace_bytes;
-    const float* wg_t; const float* bg; const float* wcx_t; const float* wch_t; const float* bc;
-    const float* wq_t; const float* bq; const float* keys; const float* values; const float* mask;
-    const float* v; const float* attn_bias;
-    const float* wo_h_t; const float* wo_e_t; const float* wo_c_t; const float* bo;
-    const float* w_vocab; int64_t ld_w_vocab; const float* b_vocab;
-    int32_t out_act, vocab_trans_b;
-    int64_t ld_cat, ld_ctx, ld_wg, ld_wcx, ld_wch, ld_wq, ld_wo_h, ld_wo_e, ld_wo_c;
-    const float* in_table; int64_t ld_table; const int32_t* in_ids;
-    void* cluster_ws; int64_t cluster_ws_bytes; uint32_t* sticky_error;
-};
-
 // nm_gru_cluster.hip: groups 1-3 of a step with input tables as ONE cluster launch; false when the shape is not taken
 bool nm_dec_step_cluster_try(hipStream_t st, int64_t R, int64_t H, int64_t A, int64_t O, const float* h_in, int64_t ld_h,
                              const float* table, int64_t ld_table, const int32_t* ids, const float* bg, const float* bq,

@@ -1169,6 +1169,59 @@ def _cluster_serialize_after(stream):
     _LAST_CLUSTER_LAUNCH[stream.device.index] = (event, stream.cuda_stream)
 
 
+def _cluster_call(name, *args):
+    """Entry point ``name`` of a cluster loop on the current stream, inside the bracket above: the only way the
+    wrappers below reach the library (a loop launched outside the bracket and another stream's loop can keep each
+    other from becoming resident)."""
+    serial = _cluster_serialize_before()
+    _lib.check(getattr(_lib.load(), name)(_stream(), *args), name)
+    _cluster_serialize_after(serial)
+
+
+def _dir_strides(w):
+    """(leading dimension, stride between directions) of a kernel [ndir, K, N], or [K, N] for one direction"""
+    w2 = w[0] if w.dim() == 3 else w
+    assert w2.stride(1) == 1
+    return w2.stride(0), (w.stride(0) if w.dim() == 3 else 0)
+
+
+def _seq_kernel(w):
+    return (w.data_ptr(),) + _dir_strides(w)
+
+
+def _seq_workspace(workspace, sticky):
+    return workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky)
+
+
+def _seq_epilogue(mode, ndir, rows, hsz, lengths, reverse_dir0):
+    """What the epilogues of all six loops share; the operands are the caller's."""
+    e = _lib.GruEpilogue()
+    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = mode, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
+    e.lengths = _p(lengths)
+    return e
+
+
+def _seq_fwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, xp, x_strides, h_in0, h_out0, out, out_strides):
+    e = _seq_epilogue(1, ndir, rows, hsz, lengths, reverse_dir0)
+    e.xp = xp.data_ptr()
+    e.x_dir, e.x_row, e.x_time = x_strides
+    e.h_in, e.h_out, e.out = _p(h_in0), h_out0.data_ptr(), _p(out)
+    e.o_dir, e.o_row, e.o_time = out_strides
+    return e
+
+
+def _seq_bwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, dh, dout, dout_strides, dxp, dxp_strides, h0=None,
+                      hseq=None, hseq_strides=(0, 0, 0)):
+    e = _seq_epilogue(4, ndir, rows, hsz, lengths, reverse_dir0)
+    e.dh, e.dout = dh.data_ptr(), _p(dout)
+    e.do_dir, e.do_row, e.do_time = dout_strides or (0, 0, 0)
+    e.dxp = dxp.data_ptr()
+    e.dx_dir, e.dx_row, e.dx_time = dxp_strides
+    e.h0, e.hseq = _p(h0), _p(hseq)
+    e.hs_dir, e.hs_row, e.hs_time = hseq_strides
+    return e
+
+
 def gru_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, ru0, ru_step, rh0, rh_step, c0,
                 c_step, wgh, wch, workspace, lengths=None, reverse_dir0=False, out=None, out_strides=(0, 0, 0),
                 sticky=None, zero_padded=False, final=None, hprev_seq=None, rh_seq=None, seq_strides=None, h0_out=None):
@@ -1181,7 +1234,6 @@ def gru_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, ru
     positions of ``out`` past a row's length; ``final`` [R, ndir*H] (row stride free): the state after each row's last
     valid step; ``hprev_seq`` / ``rh_seq`` with ``seq_strides`` (dir, row, time): h_{t-1} and r * h_{t-1} by position,
     zeros when padded; ``h0_out`` [ndir,R,H]: a copy of the initial state."""
-    lib = _lib.load()
     io = None
     if h_in0 is None or zero_padded or final is not None or hprev_seq is not None or rh_seq is not None or \
             h0_out is not None:
@@ -1193,27 +1245,14 @@ def gru_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, ru
         io.hprev_seq, io.rh_seq = _p(hprev_seq), _p(rh_seq)
         io.seq_dir, io.seq_row, io.seq_time = seq_strides or (0, 0, 0)
         io.h0_out = _p(h0_out)
-    e = _lib.GruEpilogue()
-    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 1, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
-    e.lengths = _p(lengths)
-    e.xp = xp.data_ptr()
-    e.x_dir, e.x_row, e.x_time = x_strides
-    e.h_in, e.h_out, e.ru, e.rh, e.c_save, e.out = (_p(h_in0), h_out0.data_ptr(), ru0.data_ptr(),
-                                                   _p(rh0), _p(c0), _p(out))
-    e.o_dir, e.o_row, e.o_time = out_strides
-    g2 = wgh[0] if wgh.dim() == 3 else wgh
-    c2 = wch[0] if wch.dim() == 3 else wch
-    assert g2.stride(1) == 1 and c2.stride(1) == 1
-    serial = _cluster_serialize_before()
-    tail = (steps, h_step, ru_step, rh_step, c_step,
-            wgh.data_ptr(), g2.stride(0), wgh.stride(0) if wgh.dim() == 3 else 0,
-            wch.data_ptr(), c2.stride(0), wch.stride(0) if wch.dim() == 3 else 0,
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky))
+    e = _seq_fwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, xp, x_strides, h_in0, h_out0, out, out_strides)
+    e.ru, e.rh, e.c_save = ru0.data_ptr(), _p(rh0), _p(c0)
+    tail = (steps, h_step, ru_step, rh_step, c_step, *_seq_kernel(wgh), *_seq_kernel(wch),
+            *_seq_workspace(workspace, sticky))
     if io is None:
-        _lib.check(lib.nm_gru_seq_fwd(_stream(), ctypes.byref(e), *tail), "nm_gru_seq_fwd")
+        _cluster_call("nm_gru_seq_fwd", ctypes.byref(e), *tail)
     else:
-        _lib.check(lib.nm_gru_seq_fwd_ex(_stream(), ctypes.byref(e), ctypes.byref(io), *tail), "nm_gru_seq_fwd_ex")
-    _cluster_serialize_after(serial)
+        _cluster_call("nm_gru_seq_fwd_ex", ctypes.byref(e), ctypes.byref(io), *tail)
 
 
 def gru_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, c0, c_step, h0, hseq, hseq_strides,
@@ -1225,7 +1264,6 @@ def gru_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, c0
 
     ``fused_io`` (nm_gru_seq_bwd_ex): dL/dh after the last step is ``d_final`` [R, ndir*H] (row stride free; None: zero)
     and ``dh`` is only written (``d_final_dir``: element offset of a direction's block, default H); ``zero_padded``: zeros at the positions of ``dxp`` past a row's length."""
-    lib = _lib.load()
     io = None
     if fused_io:
         io = _lib.GruSeqIo()
@@ -1236,28 +1274,14 @@ def gru_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, c0
             io.dfinal_dir = hsz if d_final_dir is None else d_final_dir
     else:
         assert d_final is None and not zero_padded
-    e = _lib.GruEpilogue()
-    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 4, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
-    e.lengths = _p(lengths)
-    e.dh, e.dout = dh.data_ptr(), _p(dout)
-    e.do_dir, e.do_row, e.do_time = dout_strides or (0, 0, 0)
-    e.ru, e.c, e.h0, e.hseq = ru0.data_ptr(), c0.data_ptr(), _p(h0), hseq.data_ptr()
-    e.hs_dir, e.hs_row, e.hs_time = hseq_strides
-    e.dxp = dxp.data_ptr()
-    e.dx_dir, e.dx_row, e.dx_time = dxp_strides
-    g2 = wgh[0] if wgh.dim() == 3 else wgh
-    c2 = wch[0] if wch.dim() == 3 else wch
-    assert g2.stride(1) == 1 and c2.stride(1) == 1
-    serial = _cluster_serialize_before()
-    tail = (steps, ru_step, c_step,
-            wgh.data_ptr(), g2.stride(0), wgh.stride(0) if wgh.dim() == 3 else 0,
-            wch.data_ptr(), c2.stride(0), wch.stride(0) if wch.dim() == 3 else 0,
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky))
+    e = _seq_bwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, dh, dout, dout_strides, dxp, dxp_strides, h0, hseq,
+                          hseq_strides)
+    e.ru, e.c = ru0.data_ptr(), c0.data_ptr()
+    tail = (steps, ru_step, c_step, *_seq_kernel(wgh), *_seq_kernel(wch), *_seq_workspace(workspace, sticky))
     if io is None:
-        _lib.check(lib.nm_gru_seq_bwd(_stream(), ctypes.byref(e), *tail), "nm_gru_seq_bwd")
+        _cluster_call("nm_gru_seq_bwd", ctypes.byref(e), *tail)
     else:
-        _lib.check(lib.nm_gru_seq_bwd_ex(_stream(), ctypes.byref(e), ctypes.byref(io), *tail), "nm_gru_seq_bwd_ex")
-    _cluster_serialize_after(serial)
+        _cluster_call("nm_gru_seq_bwd_ex", ctypes.byref(e), ctypes.byref(io), *tail)
 
 
 def lstm_seq_workspace_floats(rows, hsz, ndir) -> int:
@@ -1269,51 +1293,24 @@ def lstm_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, g
     """All ``steps`` forward steps of an LSTMCell layer in one launch (nm_lstm_seq_fwd).  ``xp`` 4H wide per direction
     (i | j | f | o), ``wh`` [ndir,H,4H]: the state half of the kernel, ``gates0`` / ``c0``: where step 0's activated gates
     and cell state are saved (step t at + t * step elements); zero initial cell state."""
-    lib = _lib.load()
-    e = _lib.GruEpilogue()
-    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 1, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
-    e.lengths = _p(lengths)
-    e.xp = xp.data_ptr()
-    e.x_dir, e.x_row, e.x_time = x_strides
-    e.h_in, e.h_out, e.ru, e.c_save, e.out = h_in0.data_ptr(), h_out0.data_ptr(), gates0.data_ptr(), c0.data_ptr(), _p(out)
-    e.o_dir, e.o_row, e.o_time = out_strides
-    ld_w, s_w = _dir_strides(wh)
-    serial = _cluster_serialize_before()
-    _lib.check(lib.nm_lstm_seq_fwd(_stream(), ctypes.byref(e), steps, h_step, g_step, c_step, wh.data_ptr(), ld_w, s_w,
-                                   float(forget_bias), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                   _p(sticky)), "nm_lstm_seq_fwd")
-    _cluster_serialize_after(serial)
+    e = _seq_fwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, xp, x_strides, h_in0, h_out0, out, out_strides)
+    e.ru, e.c_save = gates0.data_ptr(), c0.data_ptr()
+    _cluster_call("nm_lstm_seq_fwd", ctypes.byref(e), steps, h_step, g_step, c_step, *_seq_kernel(wh),
+                  float(forget_bias), *_seq_workspace(workspace, sticky))
 
 
 def lstm_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, gates0, g_step, c0, c_step, dxp, dxp_strides, wh,
                  workspace, lengths=None, reverse_dir0=False, sticky=None):
     """The BPTT loop of an LSTMCell layer in one launch (nm_lstm_seq_bwd): ``dh`` [ndir,R,H] holds dL/dh after the last
     step on entry and dL/dh_0 on exit; ``dxp`` (4H wide per direction) receives the pre-activation gradients."""
-    lib = _lib.load()
-    e = _lib.GruEpilogue()
-    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 4, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
-    e.lengths = _p(lengths)
-    e.dh, e.dout = dh.data_ptr(), _p(dout)
-    e.do_dir, e.do_row, e.do_time = dout_strides or (0, 0, 0)
+    e = _seq_bwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, dh, dout, dout_strides, dxp, dxp_strides)
     e.ru, e.c = gates0.data_ptr(), c0.data_ptr()
-    e.dxp = dxp.data_ptr()
-    e.dx_dir, e.dx_row, e.dx_time = dxp_strides
-    ld_w, s_w = _dir_strides(wh)
-    serial = _cluster_serialize_before()
-    _lib.check(lib.nm_lstm_seq_bwd(_stream(), ctypes.byref(e), steps, g_step, c_step, wh.data_ptr(), ld_w, s_w,
-                                   workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky)),
-               "nm_lstm_seq_bwd")
-    _cluster_serialize_after(serial)
+    _cluster_call("nm_lstm_seq_bwd", ctypes.byref(e), steps, g_step, c_step, *_seq_kernel(wh),
+                  *_seq_workspace(workspace, sticky))
 
 
 def nematus_seq_workspace_floats(rows, hsz, ndir) -> int:
     return _lib.load().nm_nematus_seq_workspace_bytes(rows, hsz, ndir) // 4
-
-
-def _dir_strides(w):
-    w2 = w[0] if w.dim() == 3 else w
-    assert w2.stride(1) == 1
-    return w2.stride(0), (w.stride(0) if w.dim() == 3 else 0)
 
 
 def nematus_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, ru0, ru_step, sc0, sc_step, c0,
@@ -1322,47 +1319,21 @@ def nematus_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step
     """All ``steps`` forward steps of a NematusGRUCell layer in one launch (nm_nematus_seq_fwd).  As ``gru_seq_fwd``;
     ``ug`` [ndir,H,2H] / ``uc`` [ndir,H,H]: the state projections, ``bgs`` [ndir,2H] / ``bcs`` [ndir,H] their biases,
     ``sc0``: where step 0's h.U_c + b_cs is saved."""
-    lib = _lib.load()
-    e = _lib.GruEpilogue()
-    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 1, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
-    e.lengths = _p(lengths)
-    e.xp = xp.data_ptr()
-    e.x_dir, e.x_row, e.x_time = x_strides
-    e.h_in, e.h_out, e.ru, e.rh, e.c_save, e.out = (h_in0.data_ptr(), h_out0.data_ptr(), ru0.data_ptr(),
-                                                   sc0.data_ptr(), c0.data_ptr(), _p(out))
-    e.o_dir, e.o_row, e.o_time = out_strides
-    ld_g, s_g = _dir_strides(ug)
-    ld_c, s_c = _dir_strides(uc)
-    serial = _cluster_serialize_before()
-    _lib.check(lib.nm_nematus_seq_fwd(_stream(), ctypes.byref(e), steps, h_step, ru_step, sc_step, c_step,
-                                      ug.data_ptr(), ld_g, s_g, uc.data_ptr(), ld_c, s_c, _p(bgs), _p(bcs),
-                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky)),
-               "nm_nematus_seq_fwd")
-    _cluster_serialize_after(serial)
+    e = _seq_fwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, xp, x_strides, h_in0, h_out0, out, out_strides)
+    e.ru, e.rh, e.c_save = ru0.data_ptr(), sc0.data_ptr(), c0.data_ptr()
+    _cluster_call("nm_nematus_seq_fwd", ctypes.byref(e), steps, h_step, ru_step, sc_step, c_step, *_seq_kernel(ug),
+                  *_seq_kernel(uc), _p(bgs), _p(bcs), *_seq_workspace(workspace, sticky))
 
 
 def nematus_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, sc0, sc_step, c0, c_step, h0, hseq,
                     hseq_strides, dxp, dxp_strides, ug, uc, workspace, lengths=None, reverse_dir0=False, sticky=None):
     """The BPTT loop of a NematusGRUCell layer in one launch (nm_nematus_seq_bwd); ``dxp`` is 4H wide per direction:
     [dr' | du' | dc' | dsc]."""
-    lib = _lib.load()
-    e = _lib.GruEpilogue()
-    e.mode, e.t, e.rev_mask, e.ndir, e.R, e.H = 4, 0, _rev_mask(ndir, reverse_dir0), ndir, rows, hsz
-    e.lengths = _p(lengths)
-    e.dh, e.dout = dh.data_ptr(), _p(dout)
-    e.do_dir, e.do_row, e.do_time = dout_strides or (0, 0, 0)
-    e.ru, e.rh, e.c, e.h0, e.hseq = ru0.data_ptr(), sc0.data_ptr(), c0.data_ptr(), _p(h0), hseq.data_ptr()
-    e.hs_dir, e.hs_row, e.hs_time = hseq_strides
-    e.dxp = dxp.data_ptr()
-    e.dx_dir, e.dx_row, e.dx_time = dxp_strides
-    ld_g, s_g = _dir_strides(ug)
-    ld_c, s_c = _dir_strides(uc)
-    serial = _cluster_serialize_before()
-    _lib.check(lib.nm_nematus_seq_bwd(_stream(), ctypes.byref(e), steps, ru_step, sc_step, c_step,
-                                      ug.data_ptr(), ld_g, s_g, uc.data_ptr(), ld_c, s_c,
-                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(), _p(sticky)),
-               "nm_nematus_seq_bwd")
-    _cluster_serialize_after(serial)
+    e = _seq_bwd_epilogue(ndir, rows, hsz, lengths, reverse_dir0, dh, dout, dout_strides, dxp, dxp_strides, h0, hseq,
+                          hseq_strides)
+    e.ru, e.rh, e.c = ru0.data_ptr(), sc0.data_ptr(), c0.data_ptr()
+    _cluster_call("nm_nematus_seq_bwd", ctypes.byref(e), steps, ru_step, sc_step, c_step, *_seq_kernel(ug),
+                  *_seq_kernel(uc), *_seq_workspace(workspace, sticky))
 
 
 def optimizer_chunk_table(store, regularizable, trainable, cuts=(), chunk=65536):
