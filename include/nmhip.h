@@ -56,7 +56,9 @@ uint32_t nm_crc32c(uint32_t crc, const void* data, int64_t n);
  * C[M,N] = act(op(A).op(B) + bias (+ C)); transA: A stored [K,M]; transB: B stored [N,K];
  * act 0 none / 1 tanh / 2 relu; batch > 1 strides the three operands;
  * algo 0 auto / 1 tiled-128 / 2 tiled-64 / 3 skinny / 4 background: 128x128 tiles, at most NM_GEMM_BG_WGS (1)
- * workgroups resident per CU, for a long leaf GEMM that runs beside another stream's latency-bound launches.
+ * workgroups resident per CU, for a long leaf GEMM that runs beside another stream's latency-bound launches
+ * / 5 tiled-128 with gemm_tiled's loop whatever NM_GEMM_CFG says (algo 1 and the automatic choice take the LDS-ring
+ * loop gemm_ring by default; the two give the same bits, so 5 is for comparing and timing them in one process).
  * fp32 MFMA (exact f32).
  * workspace (optional, device): split-K slabs for deep-K / few-tile shapes (weight gradients);
  * slabs are summed in a fixed order, results stay deterministic. */

@@ -54,7 +54,8 @@ struct NmSwitches {
     int gemm_swz;          // NM_GEMM_SWZ       XCD-aware tile order (1)
     bool gemm_nostore;     // NM_GEMM_NOSTORE   timing ablation: results are NOT written
     int gemm_sk;           // NM_GEMM_SK        split-K override (0 = makespan model)
-    int gemm_cfg;          // NM_GEMM_CFG       tile configuration of the large GEMMs (1)
+    int gemm_cfg;          // NM_GEMM_CFG       tile configuration of the large GEMMs: 10 = 128x128 on the LDS ring (gemm_ring),
+                           //                   1 = the same tile with gemm_tiled's loop, 2-9 = tuning variants (10)
     int gemm_chains;       // NM_GEMM_CHAINS    interleaved accumulation chains of the 64x64 tiles: 1, 2 or 4 (1)
     int gemm_cfg64;        // NM_GEMM_CFG64     tile of the products too small for 512 tiles of 128x128: 0 = 64x64 (4 waves),
                            //                   1 = 128x64, 2 = 64x128, 3 = 128x128 with 4 waves (tools/gemm_mid_sweep.py)

@@ -8,10 +8,12 @@
 //   nn/ortho_gru_cell.py:44-53                  (GRUCell kernels)
 // and their autodiff transposes (NT / TN forms).
 //
-// Two kernels:
+// Three kernels:
 //   gemm_tiled  : 64*TM x 64*TN block tile, BK=16, 4 waves (2x2), operands
 //                 staged through LDS k-major so every ds_read_b32 is
 //                 conflict-free; register prefetch of the next k-tile.
+//   gemm_ring   : the 128x128 tile (8 waves of 32x64) with three k-tiles in an
+//                 LDS ring and one barrier per k-tile; same arithmetic.
 //   gemm_skinny : M <= a few hundred (one decoder step).  One 32x32 output tile
 //                 per block, the block's KS waves split K, fragments go
 //                 global->VGPR directly (no LDS for operands), deterministic
@@ -77,6 +79,30 @@ __device__ __forceinline__ void store_tile32(const GemmArgs& g, float* __restric
     }
 }
 
+// XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs (each with its own 4 MB
+// L2): give XCD x the contiguous range [x*n/8, (x+1)*n/8) of a grouped tile order in which
+// consecutive ids sweep GROUP_M row tiles before moving to the next column tile, so the ~32
+// workgroups resident on one XCD form a compact GROUP_M x 4 block of tiles that shares its A
+// and B panels in that XCD's L2.
+__device__ __forceinline__ void tile_of_block(const GemmArgs& g, int tiles_m, int& bm, int& bn) {
+    const int npid = (int)gridDim.x;
+    int pid = (int)blockIdx.x;
+    if (g.swizzle) {
+        const int per = npid / 8, rem = npid % 8, x = pid % 8, i = pid / 8;
+        pid = x * per + (x < rem ? x : rem) + i;                 // contiguous range per XCD
+        constexpr int GROUP_M = 8;
+        const int tiles_n = npid / tiles_m;
+        const int width = GROUP_M * tiles_n;
+        const int group = pid / width, first = group * GROUP_M;
+        const int gsz = (tiles_m - first) < GROUP_M ? (tiles_m - first) : GROUP_M;
+        bm = first + (pid % width) % gsz;
+        bn = (pid % width) / gsz;
+    } else {
+        bm = pid % tiles_m;
+        bn = pid / tiles_m;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // tiled kernel
 // ---------------------------------------------------------------------------
@@ -112,30 +138,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_tiled(GemmArgs g, int tiles
     float (*Bs)[BK][LDBS] = reinterpret_cast<float (*)[BK][LDBS]>(smem + A_FLOATS);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs (each with its own 4 MB
-    // L2): give XCD x the contiguous range [x*n/8, (x+1)*n/8) of a grouped tile order in which
-    // consecutive ids sweep GROUP_M row tiles before moving to the next column tile, so the ~32
-    // workgroups resident on one XCD form a compact GROUP_M x 4 block of tiles that shares its A
-    // and B panels in that XCD's L2.
     int bm, bn;
-    {
-        const int npid = (int)gridDim.x;
-        int pid = (int)blockIdx.x;
-        if (g.swizzle) {
-            const int per = npid / 8, rem = npid % 8, x = pid % 8, i = pid / 8;
-            pid = x * per + (x < rem ? x : rem) + i;                 // contiguous range per XCD
-            constexpr int GROUP_M = 8;
-            const int tiles_n = npid / tiles_m;
-            const int width = GROUP_M * tiles_n;
-            const int group = pid / width, first = group * GROUP_M;
-            const int gsz = (tiles_m - first) < GROUP_M ? (tiles_m - first) : GROUP_M;
-            bm = first + (pid % width) % gsz;
-            bn = (pid % width) / gsz;
-        } else {
-            bm = pid % tiles_m;
-            bn = pid / tiles_m;
-        }
-    }
+    tile_of_block(g, tiles_m, bm, bn);
     const int m0 = bm * BM, n0 = bn * BN;
     const float* __restrict__ A = (g.ptrs && !CHAIN) ? g.ptrs[3 * blockIdx.z] : g.A + (long)blockIdx.z * g.sA;
     const float* __restrict__ B = (g.ptrs && !CHAIN) ? g.ptrs[3 * blockIdx.z + 1] : g.B + (long)blockIdx.z * g.sB;
@@ -472,6 +476,172 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_tiled(GemmArgs g, int tiles
 #pragma unroll
         for (int j = 0; j < TN; ++j)
             store_tile32(g, C, acc[i][j], m0 + wm + i * 32, n0 + wn + j * 32, lane);
+}
+
+// ---------------------------------------------------------------------------
+// tiled kernel, LDS ring: the 128x128x16 tile of gemm_tiled<4, 2, 1, 2, ..., 16> (8 waves of 32x64) with a main loop
+// that does not lean on neighbouring workgroups
+// ---------------------------------------------------------------------------
+// gemm_tiled's loop is barrier -> global loads -> MFMAs -> wait for the loads -> LDS stores -> wait -> barrier: a
+// workgroup alone on its CU (the tail of a 1000-workgroup grid, a residency-capped background launch) idles the
+// matrix pipe between its last MFMA of a k-tile and its first of the next.  Here three k-tiles live in LDS.
+// Iteration t stores tile t+2 (loaded a whole iteration ago) into stage (t+2)%3, requests tile t+3, runs the MFMAs
+// of tile t from stage t%3 with the first fragments of tile t+1 read under its last MFMAs, and takes ONE barrier:
+//   stage (t+2)%3 was last read in iteration t-1, which every wave left through that iteration's barrier;
+//   tile t+1 was stored in iteration t-1, before the same barrier.
+// The arithmetic is gemm_tiled's: every output element is one k-ascending MFMA chain from zero, the split-K slices,
+// the slabs and the epilogue are the same, so the results are bit for bit those of gemm_tiled<4, 2, 1, 2, ..., 16>
+// (tests/test_gemm_ring_gpu.py).  Operand bases come from the kernel arguments only (grouped and chained products
+// keep gemm_tiled), so the loads are global_load, and a k-tile step is a pointer increment.
+template <bool VEC>
+__device__ __forceinline__ float4 ring_load4(const float* __restrict__ p, bool line_ok, int c, int c_end) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (line_ok) {
+        if (VEC) { if (c < c_end) v = *reinterpret_cast<const float4*>(p); }
+        else {
+            if (c + 0 < c_end) v.x = p[0];
+            if (c + 1 < c_end) v.y = p[1];
+            if (c + 2 < c_end) v.z = p[2];
+            if (c + 3 < c_end) v.w = p[3];
+        }
+    }
+    return v;
+}
+
+static constexpr int NM_RING_LDS_BYTES = 3 * 2 * 16 * (128 + 4) * 4;       // 50 688: three workgroups per CU
+// Residency-capped background launches (nm_gemm_f32 algo 4) take the ring too: its instances stay within the 80
+// vector registers and 64 KB of own LDS that a cluster time loop beside them is budgeted against
+// (tests/test_gemm_ring_resources.py)
+static constexpr bool NM_RING_BACKGROUND = true;
+
+template <bool TA, bool TB, bool VEC>
+// (waves_per_eu 6: the register allocator keeps within 80 registers, so three workgroups share a CU like gemm_tiled's)
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void gemm_ring(GemmArgs g, int tiles_m) {
+    constexpr int BM = 128, BN = 128, BK = 16, KQ = BK / 4, TN = 2, NS = 3;
+    constexpr int LDS_ROW = BM + 4;                    // floats per k-row of a staged operand tile (A and B alike)
+    constexpr int STAGE = 2 * BK * LDS_ROW;            // floats per stage: the A tile, then the B tile
+    static_assert(NS * STAGE * 4 == NM_RING_LDS_BYTES && (BK * LDS_ROW * 4) % 16 == 0, "ring layout");
+    __shared__ __attribute__((aligned(16))) float smem[NS * STAGE];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int bm, bn;
+    tile_of_block(g, tiles_m, bm, bn);
+    const int m0 = bm * BM, n0 = bn * BN;
+    const float* __restrict__ A = g.A + (long)blockIdx.z * g.sA;
+    const float* __restrict__ B = g.B + (long)blockIdx.z * g.sB;
+    float* __restrict__ C = g.C + (long)blockIdx.z * g.sC;
+
+    // split-K: slice blockIdx.y owns the n k-tiles from kt0 on (n <= 0: an empty slice stores zeros)
+    const int nkt_all = (g.K + BK - 1) / BK;
+    const int per_slice = (nkt_all + g.splitk - 1) / g.splitk;
+    const int kt0 = blockIdx.y * per_slice;
+    const int n = min(nkt_all, kt0 + per_slice) - kt0;
+
+    // this thread's float4 of an A and of a B tile (512 threads x 4 = 128 x 16): where it comes from ...
+    const int ka = TA ? tid / (BM / 4) : (tid % KQ) * 4, ma = TA ? (tid % (BM / 4)) * 4 : tid / KQ;
+    const int kb = !TB ? tid / (BN / 4) : (tid % KQ) * 4, nb = !TB ? (tid % (BN / 4)) * 4 : tid / KQ;
+    const int gma = m0 + ma, gnb = n0 + nb;
+    int gka = kt0 * BK + ka, gkb = kt0 * BK + kb;
+    const float* pa = TA ? A + (long)gka * g.lda + gma : A + (long)gma * g.lda + gka;
+    const float* pb = !TB ? B + (long)gkb * g.ldb + gnb : B + (long)gnb * g.ldb + gkb;
+    const long step_a = TA ? BK * g.lda : BK, step_b = !TB ? BK * g.ldb : BK;
+    // ... and where it goes in a stage
+    const int sa = ka * LDS_ROW + ma, sb = BK * LDS_ROW + kb * LDS_ROW + nb;
+
+    // the next k-tile of this slice, then one tile on (the caller guards by the SLICE's tile count: a slice never
+    // touches its neighbour's k-tiles; gk < K only cuts the last tile of the product)
+    auto load_tile = [&](float4& ra, float4& rb) {
+        ra = TA ? ring_load4<VEC>(pa, gka < g.K, gma, g.M) : ring_load4<VEC>(pa, gma < g.M, gka, g.K);
+        rb = !TB ? ring_load4<VEC>(pb, gkb < g.K, gnb, g.N) : ring_load4<VEC>(pb, gnb < g.N, gkb, g.K);
+        pa += step_a; pb += step_b;
+        gka += BK; gkb += BK;
+    };
+    auto store_stage = [&](int s, const float4& ra, const float4& rb) {
+        float* S = smem + s * STAGE;
+        if (TA) *reinterpret_cast<float4*>(S + sa) = ra;
+        else {
+            S[sa + 0 * LDS_ROW] = ra.x;
+            S[sa + 1 * LDS_ROW] = ra.y;
+            S[sa + 2 * LDS_ROW] = ra.z;
+            S[sa + 3 * LDS_ROW] = ra.w;
+        }
+        if (!TB) *reinterpret_cast<float4*>(S + sb) = rb;
+        else {
+            S[sb + 0 * LDS_ROW] = rb.x;
+            S[sb + 1 * LDS_ROW] = rb.y;
+            S[sb + 2 * LDS_ROW] = rb.z;
+            S[sb + 3 * LDS_ROW] = rb.w;
+        }
+    };
+
+    f32x16 acc[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+
+    const int wm = (wave / 2) * 32, wn = (wave % 2) * 32 * TN;
+    const int fa = (lane >> 5) * LDS_ROW + wm + (lane & 31), fb = BK * LDS_ROW + (lane >> 5) * LDS_ROW + wn + (lane & 31);
+    float a[2], b[2][TN];                     // two fragment sets: the pair in the MFMAs and the pair on its way
+    auto read_frag = [&](int s, int kk, int p) {
+        const float* S = smem + s * STAGE + kk * LDS_ROW;
+        a[p] = S[fa];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[p][j] = S[fb + j * 32];
+    };
+    // the MFMAs of the k-tile in stage `cur`; its first fragment pair is in set 0 already, and set 0 leaves with the
+    // first pair of stage `nxt` (BK / 2 pairs: an even number).  After the last tile that read returns whatever the
+    // stage holds and nobody uses it.
+    auto mma_tile = [&](int cur, int nxt) {
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            const int p = (kk >> 1) & 1;
+            if (kk + 2 < BK) read_frag(cur, kk + 2, p ^ 1);
+            else read_frag(nxt, 0, p ^ 1);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[p], b[p][j], acc[j], 0, 0, 0);
+            // pin the order: the LDS reads of the next pair first, then this pair's MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x100, 1 + TN, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, TN, 0);
+        }
+    };
+
+    if (n > 0) {
+        float4 ra, rb;
+        {   // prologue: tiles 0 and 1 into stages 0 and 1 (both requested before either is stored), tile 2 requested
+            float4 ra1, rb1;
+            load_tile(ra, rb);
+            if (n > 1) load_tile(ra1, rb1);
+            store_stage(0, ra, rb);
+            if (n > 2) load_tile(ra, rb);
+            if (n > 1) store_stage(1, ra1, rb1);
+        }
+        __syncthreads();
+        read_frag(0, 0, 0);
+        int t = 0;
+        while (t < n) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {          // unrolled over the ring: every stage index is a constant
+                if (t + 2 < n) store_stage((s + 2) % NS, ra, rb);
+                if (t + 3 < n) load_tile(ra, rb);
+                mma_tile(s, (s + 1) % NS);
+                __syncthreads();
+                if (++t >= n) break;
+            }
+        }
+    }
+
+    if (g.splitk > 1) {          // raw partial sums into this slice's slab; epilogue in splitk_reduce
+        GemmArgs gs = g;
+        gs.ldc = g.N; gs.bias = nullptr; gs.act = 0; gs.accumulate = 0;
+        float* slab = g.ws + (long)blockIdx.y * g.M * g.N;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) store_tile32(gs, slab, acc[j], m0 + wm, n0 + wn + j * 32, lane);
+        return;
+    }
+    if (!g.store_c) return;             // NM_GEMM_NOSTORE timing ablation
+#pragma unroll
+    for (int j = 0; j < TN; ++j) store_tile32(g, C, acc[j], m0 + wm, n0 + wn + j * 32, lane);
 }
 
 // fixed-order sum of the split-K slabs + the GEMM epilogue (deterministic)
@@ -1190,6 +1360,28 @@ static void launch_tiled(const GemmArgs& g, int batch, bool ta, bool tb, bool ve
 #undef NM_GT
 }
 
+// the same tile through the LDS ring (gemm_ring): one instance per (ta, tb, vec)
+static void launch_ring(const GemmArgs& g, int batch, bool ta, bool tb, bool vec, hipStream_t st, int pad_lds = 0) {
+    const int tiles_m = nm_cdiv(g.M, 128), tiles_n = nm_cdiv(g.N, 128);
+    dim3 grid(tiles_m * tiles_n, g.splitk, batch), block(512);
+    static DevMask attr_devs[8];
+#define NM_GR(TA_, TB_, V_)                                                                              \
+    launch_padded(gemm_ring<TA_, TB_, V_>, attr_devs[(TA_ ? 4 : 0) + (TB_ ? 2 : 0) + (V_ ? 1 : 0)], pad_lds, grid, \
+                  block, st, g, tiles_m)
+    if (vec) {
+        if (!ta && !tb) NM_GR(false, false, true);
+        else if (!ta && tb) NM_GR(false, true, true);
+        else if (ta && !tb) NM_GR(true, false, true);
+        else NM_GR(true, true, true);
+    } else {
+        if (!ta && !tb) NM_GR(false, false, false);
+        else if (!ta && tb) NM_GR(false, true, false);
+        else if (ta && !tb) NM_GR(true, false, false);
+        else NM_GR(true, true, false);
+    }
+#undef NM_GR
+}
+
 extern "C" int nm_gemm_f32(void* stream, int transA, int transB, int64_t M, int64_t N, int64_t K,
                            const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
                            int64_t ldc, const float* bias, int act, int accumulate, int64_t batch,
@@ -1223,7 +1415,10 @@ extern "C" int nm_gemm_f32(void* stream, int transA, int transB, int64_t M, int6
     const bool b_vec = nm_aligned16(B) && ldb % 4 == 0 && strideB % 4 == 0 && ((tb ? K : N) % 4 == 0);
     const bool vec = a_vec && b_vec;
 
-    // algo: 0 auto, 1 tiled 128x128, 2 tiled 64x64, 3 skinny, 4 background
+    // algo: 0 auto, 1 tiled 128x128, 2 tiled 64x64, 3 skinny, 4 background, 5 tiled 128x128 with gemm_tiled's loop
+    // whatever NM_GEMM_CFG says (one process can then run both loops on the same operands)
+    const bool old_loop = algo == 5;
+    if (old_loop) algo = 1;
     // Background: a leaf GEMM meant to run BESIDE latency-bound launches of another stream (the vocabulary
     // projection's weight gradient next to the BPTT loops).  Left alone, the 1000 workgroups of that GEMM all become
     // resident at once -- 3 per CU, 480 of a SIMD's 512 vector registers -- and every launch of the other stream
@@ -1284,10 +1479,12 @@ extern "C" int nm_gemm_f32(void* stream, int transA, int transB, int64_t M, int6
                 if (algo == 0) pick = big ? 1 : 2;
             }
         }
-        const int cfg_env = sw.gemm_cfg;                                                      // tuning knob (1 measured best)
+        const int cfg_env = sw.gemm_cfg;                                     // tuning knob (10, the ring, measured best)
         if (pick == 1) {
             if (bg_lds > 0 && sw.gemm_bg_cfg == 2) launch_tiled<4, 2, 2, 2, 16>(g, (int)batch, ta, tb, vec, st, bg_pad(bg_lds, 50176)); // background, 256x128
-            else if (cfg_env == 1) launch_tiled<4, 2, 1, 2, 16>(g, (int)batch, ta, tb, vec, st, bg_pad(bg_lds, 33792)); // 128x128, 8 waves
+            else if (cfg_env == 10 && !old_loop && (bg_lds == 0 || NM_RING_BACKGROUND))
+                launch_ring(g, (int)batch, ta, tb, vec, st, bg_pad(bg_lds, NM_RING_LDS_BYTES));       // 128x128, 8 waves, LDS ring
+            else if (cfg_env == 1 || cfg_env == 10 || old_loop) launch_tiled<4, 2, 1, 2, 16>(g, (int)batch, ta, tb, vec, st, bg_pad(bg_lds, 33792)); // 128x128, 8 waves
             else if (cfg_env == 3) launch_tiled<4, 4, 1, 1, 32>(g, (int)batch, ta, tb, vec, st);   // 128x128, 16 waves
             else if (cfg_env == 4) launch_tiled<4, 2, 1, 2, 32>(g, (int)batch, ta, tb, vec, st);   // 128x128, 8 waves, BK 32
             else if (cfg_env == 5) launch_tiled<2, 4, 2, 1, 16>(g, (int)batch, ta, tb, vec, st);   // 128x128, 8 waves 64x32

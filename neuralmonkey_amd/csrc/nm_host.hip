@@ -29,7 +29,7 @@ static void switches_from_env(NmSwitches* sw) {
     sw->gemm_swz = env_int("NM_GEMM_SWZ", 1);
     sw->gemm_nostore = getenv("NM_GEMM_NOSTORE") != nullptr;
     sw->gemm_sk = env_int("NM_GEMM_SK", 0);
-    sw->gemm_cfg = env_int("NM_GEMM_CFG", 1);
+    sw->gemm_cfg = env_int("NM_GEMM_CFG", 10);
     sw->gemm_chains = env_int("NM_GEMM_CHAINS", 1);
     sw->gemm_cfg64 = env_int("NM_GEMM_CFG64", 0);
     sw->gemm_bg_wgs = env_int("NM_GEMM_BG_WGS", 1);
