@@ -238,6 +238,13 @@ BNSYNC_SIGNATURES = {
     "nm_bn2d_bwd_dx": (I, [P, P, L, P, L, P, L, L, L, P, P, P, F, I, P, L, P, L, I]),
 }
 
+# ... and every symbol include/nmhip_optim.h declares (the clip + update pass of GradientDescent, Momentum, Adagrad and
+# RMSProp, csrc/nm_optim_family.hip); the argument lists are nm_optim_apply's and nm_optim_apply_list's
+OPTIM_SIGNATURES = {
+    "nm_optim_update": (I, [P, I, P, P, P, P, P, P, P, P, P, P, L, L, F, F, F, F, F, L, L, P, P, L]),
+    "nm_optim_update_list": (I, [P, I, P, P, P, P, P, P, P, P, P, P, L, L, F, F, F, F, F, P, L, P, P, L]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -309,7 +316,7 @@ def load():
                               + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
                               + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
                               + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
-                              + list(BNSYNC_SIGNATURES.items())):
+                              + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

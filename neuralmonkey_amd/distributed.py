@@ -589,7 +589,8 @@ class DataParallel:
         """Everything between the backward pass and the next forward pass: gradient exchange, regulariser terms and
         per-tensor norms, clip + update, and -- sharded -- the all-gather of the updated parameters.  ``tables``: the
         optimizer's chunk tables (ops.OptimizerTables built with ``optimizer_cuts``: ``partials`` / ``partial_vector`` /
-        ``segments`` / ``apply`` / ``chunk_range``); kind 0 Adam, 1 Adadelta, ``params`` their four scalars; ``skip``:
+        ``segments`` / ``apply`` / ``chunk_range``); kind 0 Adam, 1 Adadelta, 2..5 the kinds of nmhip_optim.h (a slot such a kind lacks is
+        ``None``), ``params`` their four scalars; ``skip``:
         the device word that voids the update (its maximum over ranks is taken here).  Returns the device [L1, L2]."""
         grad = store.ensure_grad()
         self.all_reduce_gradients(store, error_word=skip)
@@ -639,11 +640,12 @@ class DataParallel:
 
     def gather_optimizer_slots(self, store, slot0, slot1) -> None:
         """Sharded optimizer: a rank holds the slots of its own slices only.  Before they are written to a checkpoint
-        (or compared in a test) every rank collects the others'."""
+        (or compared in a test) every rank collects the others'.  A slot the optimizer does not have is ``None``."""
         if self.sharded_active() and self.world_size > 1:
             plan = self.plan(store)
-            self._gather_buckets(slot0, plan)
-            self._gather_buckets(slot1, plan)
+            for slot in (slot0, slot1):
+                if slot is not None:
+                    self._gather_buckets(slot, plan)
 
     def exchange_report(self) -> dict:
         """Mean exposed wait per step since the last call (``timing`` on), bytes exchanged per step and how many of

@@ -1430,9 +1430,20 @@ class OptimizerTables:
 
     def apply(self, kind, theta, grad, slot0, slot1, clip_norm, params, skip=None, chunks=None, chunk_list=None):
         """nm_optim_apply: kind 0 Adam (lr_t, beta1, beta2, epsilon), 1 Adadelta (lr, rho, epsilon, -); ``chunks``: a
-        (begin, end) range, ``chunk_list``: a device list of chunk indices (``chunk_list()``) in one launch."""
+        (begin, end) range, ``chunk_list``: a device list of chunk indices (``chunk_list()``) in one launch.  Kinds 2..5
+        (optimizers.GradientDescentOptimizer.kind ...) are nm_optim_update's; a slot such a kind lacks is ``None``."""
         lib = _lib.load()
         p0, p1, p2, p3 = (float(x) for x in params)
+        if int(kind) >= 2:
+            c0, c1 = chunks if chunks is not None else (0, self.nchunk)
+            if chunk_list is not None:
+                name, select = "nm_optim_update_list", (chunk_list.data_ptr(), chunk_list.numel())
+            else:
+                name, select = "nm_optim_update", (int(c0), int(c1))
+            _lib.check(getattr(lib, name)(_stream(), int(kind), theta.data_ptr(), grad.data_ptr(), _p(slot0), _p(slot1),
+                                          *self._tabs(), float(clip_norm or 0.0), p0, p1, p2, p3, *select, _p(skip),
+                                          self.workspace.data_ptr(), self.workspace.numel() * 4), name)
+            return
         if chunk_list is not None:
             _lib.check(lib.nm_optim_apply_list(_stream(), int(kind), theta.data_ptr(), grad.data_ptr(), slot0.data_ptr(),
                                                slot1.data_ptr(), *self._tabs(), float(clip_norm or 0.0), p0, p1, p2, p3,

@@ -1,14 +1,18 @@
 """Optimizer descriptions (stand-ins for the tf.train.* objects INI files name).
 
-The update itself is a fused clip + Adam / Adadelta HIP kernel over the flat parameter
-buffer (csrc/nm_optim.hip); these classes only carry hyper-parameters and the names of
-the two slot variables a TensorFlow checkpoint holds per variable (``slot_suffixes``)."""
+The update itself is a fused clip + update HIP kernel over the flat parameter buffer
+(csrc/nm_optim.hip: Adam, Adadelta; csrc/nm_optim_family.hip: GradientDescent, Momentum,
+Adagrad, RMSProp); these classes only carry hyper-parameters and the names of the slot
+variables -- none, one or two -- a TensorFlow checkpoint holds per variable (``slot_suffixes``)."""
 import math
 from typing import Callable, Union
+
+from .checking import check_argument_types
 
 
 class Optimizer:
     slot_suffixes = ("/Adam", "/Adam_1")
+    slot_initial = (0.0, 0.0)          # the value each slot starts at
 
 
 class AdamOptimizer(Optimizer):
@@ -54,3 +58,89 @@ class AdadeltaOptimizer(Optimizer):
     def learning_rate(self, step: int) -> float:
         """As ``AdamOptimizer.learning_rate``: a schedule is evaluated at the global step before the update."""
         return float(self._lr(step - 1)) if callable(self._lr) else float(self._lr)
+
+
+class _FamilyOptimizer(Optimizer):
+    """What the trainer reads from the optimizers whose update is nm_optim_update (include/nmhip_optim.h):
+    ``kind`` (2..5), ``slot_suffixes`` (0, 1 or 2 names, ``<var>/<name>`` and ``<var>/<name>_1`` as TensorFlow's slot
+    creator makes them), ``slot_initial`` (the value each slot starts at) and ``params(step)``, the four scalars of
+    the update.  None of them keeps beta powers in a checkpoint."""
+    kind = -1
+    slot_suffixes = ()
+    slot_initial = ()
+
+    def learning_rate(self, step: int) -> float:
+        """As ``AdamOptimizer.learning_rate``: a schedule is evaluated at the global step before the update."""
+        return float(self._lr(step - 1)) if callable(self._lr) else float(self._lr)
+
+    def params(self, step: int):
+        raise NotImplementedError
+
+
+class GradientDescentOptimizer(_FamilyOptimizer):
+    """tf.train.GradientDescentOptimizer, TF 1.12's ApplyGradientDescent: var -= lr*g.  No slots."""
+    kind = 2
+
+    def __init__(self, learning_rate: Union[float, Callable[[int], float]], use_locking: bool = False,
+                 name: str = "GradientDescent") -> None:
+        check_argument_types()
+        self._lr = learning_rate
+
+    def params(self, step: int):
+        return (self.learning_rate(step), 0.0, 0.0, 0.0)
+
+
+class MomentumOptimizer(_FamilyOptimizer):
+    """tf.train.MomentumOptimizer, TF 1.12's ApplyMomentum: accum = accum*momentum + g; var -= lr*accum, or with
+    ``use_nesterov`` var -= g*lr + accum*momentum*lr (the new accum).  One slot, ``<var>/<name>``, starting at 0."""
+    kind = 3
+
+    def __init__(self, learning_rate: Union[float, Callable[[int], float]], momentum: float,
+                 use_locking: bool = False, name: str = "Momentum", use_nesterov: bool = False) -> None:
+        check_argument_types()
+        self._lr = learning_rate
+        self.momentum, self.use_nesterov = float(momentum), use_nesterov
+        self.slot_suffixes = ("/" + name,)
+        self.slot_initial = (0.0,)
+
+    def params(self, step: int):
+        return (self.learning_rate(step), self.momentum, 1.0 if self.use_nesterov else 0.0, 0.0)
+
+
+class AdagradOptimizer(_FamilyOptimizer):
+    """tf.train.AdagradOptimizer, TF 1.12's ApplyAdagrad: accum += g*g; var -= g*lr*rsqrt(accum) -- no epsilon.  One
+    slot, ``<var>/<name>``, starting at ``initial_accumulator_value``."""
+    kind = 4
+
+    def __init__(self, learning_rate: Union[float, Callable[[int], float]], initial_accumulator_value: float = 0.1,
+                 use_locking: bool = False, name: str = "Adagrad") -> None:
+        check_argument_types()
+        if initial_accumulator_value <= 0.0:
+            raise ValueError("initial_accumulator_value must be positive: {}".format(initial_accumulator_value))
+        self._lr = learning_rate
+        self.initial_accumulator_value = float(initial_accumulator_value)
+        self.slot_suffixes = ("/" + name,)
+        self.slot_initial = (self.initial_accumulator_value,)
+
+    def params(self, step: int):
+        return (self.learning_rate(step), 0.0, 0.0, 0.0)
+
+
+class RMSPropOptimizer(_FamilyOptimizer):
+    """tf.train.RMSPropOptimizer, TF 1.12's ApplyRMSProp: ms += (g*g - ms)*(1-decay); mom = mom*momentum +
+    (g*lr)/sqrt(ms + epsilon); var -= mom.  Two slots: ``<var>/<name>`` (rms, starting at ONE) and ``<var>/<name>_1``
+    (momentum, starting at 0).  ``centered=True`` (a third slot, the mean gradient) constructs and is refused by the
+    trainer that takes it."""
+    kind = 5
+
+    def __init__(self, learning_rate: Union[float, Callable[[int], float]], decay: float = 0.9, momentum: float = 0.0,
+                 epsilon: float = 1e-10, use_locking: bool = False, centered: bool = False,
+                 name: str = "RMSProp") -> None:
+        check_argument_types()
+        self._lr = learning_rate
+        self.decay, self.momentum, self.epsilon, self.centered = float(decay), float(momentum), float(epsilon), centered
+        self.slot_suffixes = ("/" + name, "/" + name + "_1")
+        self.slot_initial = (1.0, 0.0)
+
+    def params(self, step: int):
+        return (self.learning_rate(step), self.decay, self.momentum, self.epsilon)

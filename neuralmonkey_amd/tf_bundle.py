@@ -312,19 +312,19 @@ def export_store(store, prefix: str, global_step: Optional[int] = None, with_ada
     # global variables expects their keys -- and, being trainable, their Adam slots
     extras = store.checkpoint_only_values()
     tensors.update(extras)
-    s0, s1 = store.slot_suffixes
-    if with_adam and store.adam_m is not None:
+    # one slot variable per name in ``slot_suffixes``: two (Adam, Adadelta, RMSProp), one (Momentum, Adagrad) or none
+    slots = list(zip(store.slot_suffixes, [s.cpu().numpy() for s in store.slots()]))
+    if with_adam and slots:
         for name, arr in extras.items():
-            tensors[name + s0] = np.zeros_like(arr)
-            tensors[name + s1] = np.zeros_like(arr)
-        m, v = store.adam_m.cpu().numpy(), store.adam_v.cpu().numpy()
+            for suffix, _ in slots:
+                tensors[name + suffix] = np.zeros_like(arr)
         for name, spec in store.specs.items():
             if not spec.trainable:         # no optimizer makes slots for them (batch norm's moving statistics)
                 continue
             shape = tf_shape(name, spec.shape)
-            tensors[name + s0] = m[spec.offset:spec.offset + spec.size].reshape(shape)
-            tensors[name + s1] = v[spec.offset:spec.offset + spec.size].reshape(shape)
-        if s0 == "/Adam":                  # Adam's two non-slot variables; Adadelta has none
+            for suffix, slot in slots:
+                tensors[name + suffix] = slot[spec.offset:spec.offset + spec.size].reshape(shape)
+        if slots[0][0] == "/Adam" and len(slots) == 2:         # Adam's two non-slot variables; no other optimizer has any
             step = global_step or 0
             tensors["beta1_power"] = np.float32(beta1 ** (step + 1))
             tensors["beta2_power"] = np.float32(beta2 ** (step + 1))
@@ -349,21 +349,11 @@ def import_store(store, prefix: str, strict: bool = True) -> Dict[str, object]:
     if strict and missing:
         raise KeyError("variables missing from the checkpoint: {}".format(missing[:8]))
     store.load_state_dict(values, strict=False)
-    from .variables import find_slot_suffixes
     slotted = [n for n in values if store.specs[n].trainable]        # non-trainable variables have no slots
-    s0, s1 = store.slot_suffixes = find_slot_suffixes(bundle, slotted, store.slot_suffixes)
-    if all(n + s0 in bundle and n + s1 in bundle for n in slotted) and slotted:
-        import torch
-        m, v = store.ensure_adam()
-        for name in slotted:
-            spec = store.specs[name]
-            m[spec.offset:spec.offset + spec.size] = torch.from_numpy(
-                np.asarray(bundle[name + s0], np.float32).reshape(-1)).to(m.device)
-            v[spec.offset:spec.offset + spec.size] = torch.from_numpy(
-                np.asarray(bundle[name + s1], np.float32).reshape(-1)).to(v.device)
+    suffixes = store.take_slots(bundle, slotted)                     # none, one or two per variable
     extras = store.take_checkpoint_only(bundle)
     known = set(values) | set(extras)
-    known |= {n + s for n in known for s in (s0, s1)}
+    known |= {n + s for n in known for s in suffixes}
     step = bundle.get("global_step")
     return {"missing": missing, "unused": sorted(set(bundle) - known - {"global_step", "beta1_power", "beta2_power"}),
             "global_step": None if step is None else int(step)}

@@ -27,7 +27,10 @@ tanh = _activation("tanh")
 identity = _activation("identity")
 nn = SimpleNamespace(relu=_activation("relu"), tanh=tanh)
 
-train = SimpleNamespace(AdamOptimizer=_opt.AdamOptimizer, AdadeltaOptimizer=_opt.AdadeltaOptimizer)
+train = SimpleNamespace(AdamOptimizer=_opt.AdamOptimizer, AdadeltaOptimizer=_opt.AdadeltaOptimizer,
+                        GradientDescentOptimizer=_opt.GradientDescentOptimizer,
+                        MomentumOptimizer=_opt.MomentumOptimizer, AdagradOptimizer=_opt.AdagradOptimizer,
+                        RMSPropOptimizer=_opt.RMSPropOptimizer)
 contrib = SimpleNamespace(opt=SimpleNamespace(LazyAdamOptimizer=_opt.LazyAdamOptimizer))
 initializers = SimpleNamespace(random_uniform=random_uniform_initializer,
                                random_normal=random_normal_initializer, zeros=zeros_initializer,

@@ -15,7 +15,8 @@ import torch
 
 from .. import ops
 from ..model.model_part import Feedable
-from ..optimizers import AdadeltaOptimizer, AdamOptimizer, Optimizer
+from ..optimizers import (AdadeltaOptimizer, AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer,
+                          MomentumOptimizer, Optimizer, RMSPropOptimizer)
 from ..runners.base_runner import GraphExecutor, LazyLosses, NextExecute
 from ..runtime import HostPending, RunContext, tensor
 from .objective import Objective
@@ -64,9 +65,13 @@ class GenericTrainer(GraphExecutor, Feedable):
         self.var_scopes = var_scopes
         self.var_collection = var_collection
         self.optimizer = optimizer if optimizer is not None else self.default_optimizer()
-        if not isinstance(self.optimizer, (AdamOptimizer, AdadeltaOptimizer)):
-            raise NotImplementedError("the HIP trainer implements Adam / LazyAdam / Adadelta; got {}"
-                                      .format(type(self.optimizer).__name__))
+        if not isinstance(self.optimizer, (AdamOptimizer, AdadeltaOptimizer, GradientDescentOptimizer,
+                                           MomentumOptimizer, AdagradOptimizer, RMSPropOptimizer)):
+            raise NotImplementedError("the HIP trainer implements Adam / LazyAdam / Adadelta / GradientDescent / "
+                                      "Momentum / Adagrad / RMSProp; got {}".format(type(self.optimizer).__name__))
+        if getattr(self.optimizer, "centered", False):
+            raise NotImplementedError("RMSPropOptimizer(centered=True) keeps a third slot per variable (the mean "
+                                      "gradient), which the HIP trainer does not implement: centered = False only")
         if clip_norm is not None and clip_norm <= 0.0:
             raise ValueError("clip_norm must be positive")
         for obj in objectives:
@@ -225,6 +230,8 @@ class GenericTrainer(GraphExecutor, Feedable):
         opt = self.optimizer
         if isinstance(opt, AdadeltaOptimizer):
             kind, params = 1, (opt.learning_rate(sess.global_step), opt.rho, opt.epsilon, 0.0)
+        elif not isinstance(opt, AdamOptimizer):         # GradientDescent, Momentum, Adagrad, RMSProp describe themselves
+            kind, params = opt.kind, opt.params(sess.global_step)
         else:
             kind, params = 0, (opt.lr_t(sess.global_step, state["applied"]), opt.beta1, opt.beta2, opt.epsilon)
         # the update is a no-op on the device while the session's error word is set (a time loop of this step gave up:
@@ -255,34 +262,39 @@ class GenericTrainer(GraphExecutor, Feedable):
             state["applied"] = snap if snap is not None else sess.global_step
 
     def _adam_state(self, sess, store):
-        """The optimizer's two slots per variable (Adam: m, v; Adadelta: accum, accum_update) and the number of
+        """The optimizer's slots per variable (Adam: m, v; Adadelta: accum, accum_update; RMSProp: rms, momentum;
+        Momentum, Adagrad: one accumulator and ``None``; GradientDescent: ``None`` twice) and the number of
         updates THIS optimizer has applied.  TensorFlow keeps one set of
         slots and one pair of beta powers per optimizer, while ``global_step`` is shared: an experiment
         with two trainers (tests/bahdanau.ini: ``trainer=[<mt_trainer>, <greedy_trainer>]``) advances the
         global step twice per batch but each optimizer's bias correction once.  The first trainer to
         update a store uses the store's own slots (the ones checkpoints carry) and continues from its
-        global step; any further trainer gets private slots starting at zero."""
+        global step; any further trainer gets private slots starting at its optimizer's
+        ``slot_initial``."""
         key = id(store)
         state = self.__dict__.setdefault("_adam", {}).get(key)
         if state is None:
             owners = sess.__dict__.setdefault("_adam_owner", {})
             if owners.setdefault(key, self) is self:
                 had_slots = store.adam_m is not None
-                m, v = store.ensure_adam()
                 mine = tuple(self.optimizer.slot_suffixes)
-                if had_slots and tuple(store.slot_suffixes) != mine:
-                    # a checkpoint written by ANOTHER optimizer (Adam's signed first moment is not an Adadelta
-                    # accumulator: sqrt(accum + eps) would go NaN).  TensorFlow's Saver refuses such a restore (the
-                    # slot variables it looks for are missing); here the variables stay and the slots start afresh.
+                initial = tuple(self.optimizer.slot_initial)
+                # a checkpoint written by ANOTHER optimizer (Adam's signed first moment is not an Adadelta
+                # accumulator: sqrt(accum + eps) would go NaN).  TensorFlow's Saver refuses such a restore (the
+                # slot variables it looks for are missing); here the variables stay and the slots start afresh.
+                foreign = had_slots and tuple(store.slot_suffixes) != mine
+                if foreign:
                     import warnings
                     warnings.warn("optimizer slots {} of the restored checkpoint do not belong to {} (slots {}): they "
-                                  "are reset to zero".format(store.slot_suffixes, type(self.optimizer).__name__, mine))
-                    ops.zero(m)
-                    ops.zero(v)
+                                  "are reset to their initial values {}"
+                                  .format(store.slot_suffixes, type(self.optimizer).__name__, mine, initial))
+                # only the slots the optimizer has (GradientDescent: no buffer at all), each starting at its own value
+                m, v = store.ensure_slots(initial, reset=foreign)
                 store.slot_suffixes = mine                                    # the slots' names in checkpoints
                 applied = sess.global_step
             else:
-                m, v = torch.zeros_like(store.theta), torch.zeros_like(store.theta)
+                m, v = (list(torch.full_like(store.theta, value) for value in self.optimizer.slot_initial)
+                        + [None, None])[:2]
                 applied = 0
             state = self._adam[key] = {"m": m, "v": v, "applied": applied}
         return state

@@ -69,19 +69,28 @@ class VarSpec:
 
 
 def find_slot_suffixes(keys, names, preferred):
-    """The names under which a checkpoint holds the optimizer's two slots of every variable: ``preferred`` when
+    """The names under which a checkpoint holds the optimizer's slots of every variable: ``preferred`` when
     present, else whatever pair ``<var>/<opt>``, ``<var>/<opt>_1`` all of ``names`` carry (a checkpoint is read
-    before the trainer that owns the slots has taken its first step and named them)."""
+    before the trainer that owns the slots has taken its first step and named them), else the single ``<var>/<opt>``
+    all of them carry (Momentum, Adagrad).  A checkpoint without slots (GradientDescent, or written before the first
+    update) leaves ``preferred``: the caller finds none of its names and reads no slots."""
     names = list(names)
-    if not names or all(n + preferred[0] in keys and n + preferred[1] in keys for n in names):
+    if not names or all(n + s in keys for n in names for s in preferred):
         return preferred
     first = names[0] + "/"
+    single = None
     for key in keys:
-        if key.startswith(first) and "/" not in key[len(first):] and key + "_1" in keys:
-            pair = ("/" + key[len(first):], "/" + key[len(first):] + "_1")
-            if all(n + pair[0] in keys and n + pair[1] in keys for n in names):
-                return pair
-    return preferred
+        if key.startswith(first) and "/" not in key[len(first):] and key not in names:
+            found = ("/" + key[len(first):],)
+            if key + "_1" in keys:
+                found += (found[0] + "_1",)
+            elif key.endswith("_1") and key[:-2] in keys:
+                continue                   # the second of a pair
+            if all(n + s in keys for n in names for s in found):
+                if len(found) == 2:
+                    return found
+                single = single or found
+    return single or preferred
 
 
 class VariableStore:
@@ -95,8 +104,8 @@ class VariableStore:
         self.specs: "OrderedDict[str, VarSpec]" = OrderedDict()
         self.theta: Optional[torch.Tensor] = None
         self.grad: Optional[torch.Tensor] = None
-        self.adam_m: Optional[torch.Tensor] = None      # the optimizer's two slots per variable (Adam: m, v;
-        self.adam_v: Optional[torch.Tensor] = None      # Adadelta: accum, accum_update) ...
+        self.adam_m: Optional[torch.Tensor] = None      # the optimizer's slots per variable (Adam: m, v; Adadelta:
+        self.adam_v: Optional[torch.Tensor] = None      # accum, accum_update; one or none: ``ensure_slots``) ...
         self.slot_suffixes = ("/Adam", "/Adam_1")       # ... and their names in a checkpoint (Optimizer.slot_suffixes)
         self.total = 0
         self.epoch = 0          # bumped by whoever writes the variables through raw pointers (Session.variables_changed)
@@ -192,10 +201,44 @@ class VariableStore:
         return self._gviews[name]
 
     def ensure_adam(self):
+        """Two slots starting at zero (Adam, Adadelta) -- or whatever slots the store holds already."""
         if self.adam_m is None:
-            self.adam_m = torch.zeros(self.total, dtype=torch.float32, device=self.device)
-            self.adam_v = torch.zeros(self.total, dtype=torch.float32, device=self.device)
+            self.ensure_slots((0.0, 0.0))
         return self.adam_m, self.adam_v
+
+    def slots(self):
+        """The slot buffers that exist, in the order of ``slot_suffixes``: none, (slot0,) or (slot0, slot1)."""
+        return tuple(s for s in (self.adam_m, self.adam_v) if s is not None)
+
+    def ensure_slots(self, initial=(0.0, 0.0), reset=False):
+        """The slot buffers of an optimizer with ``len(initial)`` slots per variable (0, 1 or 2): ``(slot0, slot1)``
+        with ``None`` for a slot it does not have.  A buffer that is missing is created filled with its entry of
+        ``initial`` (Adagrad's accumulator starts at 0.1, RMSProp's rms at one); one the optimizer does not have is
+        dropped; ``reset`` refills the ones that exist already."""
+        held = [self.adam_m, self.adam_v]
+        for i in range(2):
+            if i >= len(initial):
+                held[i] = None
+            elif held[i] is None:
+                held[i] = torch.full((self.total,), float(initial[i]), dtype=torch.float32, device=self.device)
+            elif reset:
+                held[i].fill_(float(initial[i]))
+        self.adam_m, self.adam_v = held
+        return self.adam_m, self.adam_v
+
+    def take_slots(self, values, names):
+        """Read the optimizer slots of the variables ``names`` from ``values`` (key -> array) when it holds them for
+        every one: ``slot_suffixes`` becomes the names found (``find_slot_suffixes``) and exactly that many slot
+        buffers exist afterwards.  Values that lack them leave the store's slots alone.  Returns the suffixes."""
+        suffixes = self.slot_suffixes = tuple(find_slot_suffixes(values, names, self.slot_suffixes))
+        if names and suffixes and all(n + s in values for n in names for s in suffixes):
+            slots = self.ensure_slots((0.0,) * len(suffixes))
+            for suffix, slot in zip(suffixes, slots):
+                for n in names:
+                    spec = self.specs[n]
+                    slot[spec.offset:spec.offset + spec.size] = torch.from_numpy(
+                        np.asarray(values[n + suffix], np.float32).reshape(-1)).to(slot.device)
+        return suffixes
 
     # -- (de)serialisation: npz keyed by the TF-style variable names ---------
     def state_dict(self) -> Dict[str, np.ndarray]:
@@ -227,13 +270,14 @@ class VariableStore:
             return
         arrays = {k.replace("/", "|"): v for k, v in self.state_dict().items()}
         arrays.update({k.replace("/", "|"): v for k, v in self.checkpoint_only_values().items()})
-        if self.adam_m is not None:
-            m, v = self.adam_m.cpu().numpy(), self.adam_v.cpu().numpy()
-            for name, spec in self.specs.items():
-                if not spec.trainable:     # no optimizer makes slots for them (batch norm's moving statistics)
-                    continue
-                arrays[(name + self.slot_suffixes[0]).replace("/", "|")] = m[spec.offset:spec.offset + spec.size].reshape(spec.shape)
-                arrays[(name + self.slot_suffixes[1]).replace("/", "|")] = v[spec.offset:spec.offset + spec.size].reshape(spec.shape)
+        # (one slot variable per name in ``slot_suffixes``: two for Adam, Adadelta and RMSProp, one for Momentum and
+        # Adagrad, none for GradientDescent)
+        slots = list(zip(self.slot_suffixes, [s.cpu().numpy() for s in self.slots()]))
+        for name, spec in self.specs.items() if slots else ():
+            if not spec.trainable:     # no optimizer makes slots for them (batch norm's moving statistics)
+                continue
+            for suffix, slot in slots:
+                arrays[(name + suffix).replace("/", "|")] = slot[spec.offset:spec.offset + spec.size].reshape(spec.shape)
         if global_step is not None:
             arrays["global_step"] = np.int64(global_step)
         np.savez(path, **arrays)
@@ -252,14 +296,6 @@ class VariableStore:
         self.load_state_dict(values, strict)
         self.take_checkpoint_only(values)
         names = [n for n in self.specs if n in values and self.specs[n].trainable]
-        s0, s1 = self.slot_suffixes = find_slot_suffixes(values, names, self.slot_suffixes)
-        if names and all(n + s0 in values and n + s1 in values for n in names):
-            m, v = self.ensure_adam()
-            for n in names:
-                spec = self.specs[n]
-                m[spec.offset:spec.offset + spec.size] = torch.from_numpy(
-                    np.asarray(values[n + s0], np.float32).reshape(-1)).to(m.device)
-                v[spec.offset:spec.offset + spec.size] = torch.from_numpy(
-                    np.asarray(values[n + s1], np.float32).reshape(-1)).to(v.device)
+        self.take_slots(values, names)
         step = values.get("global_step")
         return {"global_step": None if step is None else int(step)}
