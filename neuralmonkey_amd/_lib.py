@@ -245,6 +245,13 @@ OPTIM_SIGNATURES = {
     "nm_optim_update_list": (I, [P, I, P, P, P, P, P, P, P, P, P, P, L, L, F, F, F, F, F, P, L, P, P, L]),
 }
 
+# ... and every symbol include/nmhip_align.h declares (supervised attention: the rows of WordAlignmentDecoder,
+# csrc/nm_align.hip)
+ALIGN_SIGNATURES = {
+    "nm_align_xent": (I, [P, P, L, L, L, P, L, L, P, P, P, P, I]),
+    "nm_align_softmax": (I, [P, P, L, L, L, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -316,7 +323,8 @@ def load():
                               + list(CONVS2S_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
                               + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
                               + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
-                              + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())):
+                              + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
+                              + list(ALIGN_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

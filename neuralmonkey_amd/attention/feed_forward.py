@@ -138,12 +138,15 @@ class Attention(BaseAttention):
                                 self.var(ctx, "attn_bias"), ctx_all, w_all, ws, e_all)
 
     def backward(self, ctx, dctx_all: torch.Tensor, queries: torch.Tensor, y_all: torch.Tensor,
-                 w_all: torch.Tensor, e_all: torch.Tensor, dquery_accum: torch.Tensor) -> torch.Tensor:
+                 w_all: torch.Tensor, e_all: torch.Tensor, dquery_accum: torch.Tensor,
+                 alignment_terms=None) -> torch.Tensor:
         """Gradient of T attention steps at once (nothing here feeds the recurrence).
 
         dctx_all [T,B,C], queries [T,B,Q], y_all [T,B,A], w_all / e_all [T,B,S].
         Adds dL/dquery into ``dquery_accum`` [T*B,Q], accumulates this part's
-        variable gradients and returns dL/d(attention_states) [B,S,C]."""
+        variable gradients and returns dL/d(attention_states) [B,S,C].  ``alignment_terms``: losses that read the
+        weights themselves (decoders/word_alignment_decoder.py); each adds its gradient to the weights' gradient
+        between the product that writes it and the softmax's backward."""
         store = ctx.store
         states, hf, mask = self.attention_states(ctx), self.hidden_features(ctx), self.attention_mask(ctx)
         bsz, slen, c = states.shape
@@ -156,6 +159,9 @@ class Attention(BaseAttention):
         dctx_b = dctx_all.permute(1, 0, 2)                                   # [B,T,C] strided view
         ops.gemm(dctx_b, states, out=dw.permute(1, 0, 2), trans_b=True)      # dw[t,b,:] = dctx[t,b,:].states[b]^T
         ops.gemm(w_all.permute(1, 0, 2), dctx_b, out=dstates, trans_a=True)  # dstates[b] = w[:,b,:]^T.dctx[:,b,:]
+        for term in alignment_terms or ():
+            term.rows(w_all, 0, dw=dw, accumulate=True)
+            term.finish()
         de = ctx.buffer(key + ("de",), (steps, bsz, slen))
         ops.attn_softmax_bwd(dw, e_all, mask, de, bsz)
         ops.reduce_sum(de.view(-1), ctx.buffer(key + ("dbias",), (1,)))
@@ -275,6 +281,7 @@ class AttentionTapeSession:
         self.v = tape.param(att, "attn_similarity_v")
         self.bias = tape.param(att, "attn_bias")
         self._dvp = None
+        self.alignment_terms = ()          # (decoders/decoder_general.py: losses over this run's weights, step by step)
 
         def finish():           # recorded first => runs after every step's gradient closure
             if self._dvp is not None:
@@ -309,6 +316,7 @@ class AttentionTapeSession:
             if self._stack is None:
                 self._stack = (tape.buf((ENERGY_STACK, b, s)), tape.buf((ENERGY_STACK, b, a)))
             slot = self._steps
+        index = self._steps
         self._steps += 1
         y = F.linear(tape, query, self.wq, self.bq,
                      out=None if slot is None else F.Var(self._stack[1][slot], None, True))
@@ -322,14 +330,20 @@ class AttentionTapeSession:
 
         def bwd():
             dctx = out.grad
-            if dctx is None:
+            terms = self.alignment_terms
+            if dctx is None and not terms:
                 return
             assert rows == b, "the attention gradient is defined for one query per sentence"
-            fused = (STEP_BWD_FUSED and slot is not None and ops.attn_step_bwd_ok(dctx, c))
+            # (the fused kernel derives the weights' gradient from dctx itself: a step with a term on its weights takes
+            # the product + softmax-backward route, where that gradient is in memory between the two)
+            fused = (STEP_BWD_FUSED and slot is not None and not terms and ops.attn_step_bwd_ok(dctx, c))
             if not fused:
                 dw = tape.buf((b, 1, s))
-                ops.gemm(dctx.view(b, 1, c), st3, out=dw, trans_b=True)
-            if self.states.needs_grad:
+                if dctx is not None:
+                    ops.gemm(dctx.view(b, 1, c), st3, out=dw, trans_b=True)
+                for i, term in enumerate(terms):
+                    term.rows(w.view(1, b, s), index, dw=dw.view(1, b, s), accumulate=dctx is not None or i > 0)
+            if self.states.needs_grad and dctx is not None:
                 if F.CHAIN_WGRADS and dctx.is_cuda and s * ops.OUTER_CHAIN_MAX * 4 <= 65536 and b < 65536:
                     self._outer.append((w, dctx))
                 else:

@@ -5,3 +5,4 @@ from .ctc_decoder import CTCDecoder                       # noqa: F401
 from .sequence_labeler import EmbeddingsLabeler, SequenceLabeler  # noqa: F401
 from .classifier import Classifier                       # noqa: F401
 from .sequence_regressor import SequenceRegressor        # noqa: F401
+from .word_alignment_decoder import WordAlignmentDecoder  # noqa: F401

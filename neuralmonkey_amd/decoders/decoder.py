@@ -172,6 +172,21 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
         self.output_projection.declare_variables(
             self, store, h, e, [a.context_vector_size for a in self.attentions])
 
+    def get_attention_object(self, encoder, train_mode: bool = False) -> BaseAttention:
+        """The attention of this decoder that reads ``encoder`` -- what WordAlignmentDecoder asks for
+        (decoders/word_alignment_decoder.py:88; the reference calls this method and defines it nowhere).  The one
+        member of ``attentions`` whose ``encoder`` is that object, whatever ``train_mode`` is: the teacher-forced and
+        the runtime loop query the same attention objects here."""
+        found = [att for att in self.attentions if getattr(att, "encoder", None) is encoder]
+        if len(found) != 1:
+            raise ValueError("Decoder '{}' has {} attentions over the encoder '{}', exactly one is needed"
+                             .format(self.name, len(found) if found else "no", getattr(encoder, "name", encoder)))
+        return found[0]
+
+    def _alignment_terms(self, ctx, attention) -> list:
+        """The supervised-attention terms (WordAlignmentDecoder.attach) a trainer hung on ``attention`` for this run."""
+        return [term for term in ctx.memo.get((id(self), "alignment_terms"), ()) if term.attention is attention]
+
     def _cell(self, ctx):
         pre = "attention_decoder/OrthoGRUCell"
         e = self.embedding_size
@@ -340,6 +355,12 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
         for i, att in enumerate(self.attentions):
             att.attention_all_steps(ctx, s_all, y_all[i], att_states[i].contexts, att_states[i].weights, e_all[i])
         att_states = [AttentionLoopState(st.contexts, st.weights, steps) for st in att_states]
+        for att, st in zip(self.attentions, att_states):
+            # supervised attention (a trainer's term, so a backward pass is to come): the shapes are known, every check
+            # is made here; the term's one launch runs in ``Attention.backward``, where it also adds its gradient to
+            # the weights' gradient
+            for term in self._alignment_terms(ctx, att):
+                term.begin(ctx, st.weights, tmask)
 
         out_all = ctx.buffer(key + ("out",), (rows, self.output_dimension))
         self.output_projection.apply(ctx, self, s_all.view(rows, h), emb_all.view(rows, e),
@@ -456,8 +477,10 @@ class Decoder(GeneralDecoderMixin, AutoregressiveDecoder):
         d_att_states = []
         for i, att in enumerate(self.attentions):
             st = sv["att_states"][i]
+            terms = self._alignment_terms(ctx, att)
             d_att_states.append(att.backward(ctx, d_ctx[i].view(steps, bsz, -1), sv["s_all"], sv["y_all"][i],
-                                             st.weights, sv["e_all"][i], d_s))
+                                             st.weights, sv["e_all"][i], d_s,
+                                             **({"alignment_terms": terms} if terms else {})))
         if not early_dw:
             with side(1):
                 vocabulary_projection_gradient()

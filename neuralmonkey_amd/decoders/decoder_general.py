@@ -175,6 +175,15 @@ class GeneralDecoderMixin:
         s0 = F.dropout(tape, s0, keep, train, ctx.salt(self.name, "initial_state"))      # :235-240
         sessions = [a.tape_session(tape, train) for a in self.attentions]
         att_states = [a.initial_loop_state(ctx, bsz, steps, precompute=False) for a in self.attentions]
+        # supervised attention (decoders/word_alignment_decoder.py): every step's backward closure adds the term's gradient
+        # to its weights' gradient; the rows' sum is taken by a closure recorded HERE, which runs after all of them
+        for att, sess, st in zip(self.attentions, sessions, att_states):
+            mine = self._alignment_terms(ctx, att)
+            for term in mine:
+                term.begin(ctx, st.weights[:steps], tmask)
+            if mine:
+                sess.alignment_terms = mine
+                tape.record(lambda mine=mine: [term.finish() for term in mine])
         state = [s0, s0] + [tape.leaf(tape.buf((bsz, a.context_vector_size), zero=True))
                             for a in self.attentions]
         # The output projection reads the step's cell output, input embedding and contexts and feeds nothing back into

@@ -1775,6 +1775,49 @@ def label_rows(logits, targets=None, pad_id=0, grad_scale=None, write_grad=False
                                _p(grad_scale), 1, 0.0), "nm_xent")
 
 
+# ---- supervised attention (include/nmhip_align.h, csrc/nm_align.hip) ----------------------------------------------------
+def _tbs(w, what):
+    """(T, B, S) of dense time-major attention weights."""
+    _f32(w)
+    assert w.dim() == 3 and (w.numel() == 0 or w.is_contiguous()), what + ": dense [T, B, S]"
+    return tuple(w.shape)
+
+
+def align_xent(w, target, pad, loss_rows, scale=None, dw=None, accumulate=False):
+    """The rows of WordAlignmentDecoder's training loss (decoders/word_alignment_decoder.py:100-108) in one launch:
+    ``loss_rows`` [T, B] = pad * softmax_cross_entropy_with_logits(labels = target[b, t, :S], logits = w[t, b, :]) over the
+    attention weights ``w`` [T, B, S]; with ``dw`` [T, B, S] also scale[0] * pad * (softmax(w) - label), TensorFlow's
+    registered gradient, written or (``accumulate``) added.  ``target`` is the batch-major fed array [B, T', S'] with
+    T' >= T and S' >= S, read in place through its strides: rows t >= T and columns s >= S are never read."""
+    steps, bsz, slen = _tbs(w, "align_xent w")
+    _f32(target)
+    assert target.dim() == 3 and target.shape[0] == bsz and target.shape[1] >= steps and target.shape[2] >= slen, \
+        (tuple(target.shape), (steps, bsz, slen))
+    assert target.shape[2] == 1 or target.stride(2) == 1, "align_xent target: unit source stride"
+    st = target.stride(1) if target.shape[1] > 1 else max(target.stride(1), target.shape[2])
+    sb = target.stride(0) if bsz > 1 else max(target.stride(0), target.shape[1] * st)
+    for t, n in ((pad, "pad"), (loss_rows, "loss_rows")):
+        assert _f32(t).numel() == steps * bsz and (t.numel() == 0 or t.is_contiguous()), n
+    if dw is not None:
+        assert _tbs(dw, "align_xent dw") == (steps, bsz, slen)
+    if scale is not None:
+        assert _f32(scale).numel() == 1
+    _lib.check(_lib.load().nm_align_xent(_stream(), w.data_ptr(), steps, bsz, slen, target.data_ptr(), sb, st,
+                                         pad.data_ptr(), _p(scale), loss_rows.data_ptr(), _p(dw),
+                                         int(bool(accumulate))), "nm_align_xent")
+    return loss_rows
+
+
+def align_softmax(w, out):
+    """out [B, T, S] = softmax(w [T, B, S]) over the source positions, batch-major (word_alignment_decoder.py:91-97)."""
+    steps, bsz, slen = _tbs(w, "align_softmax w")
+    _f32(out)
+    assert tuple(out.shape) == (bsz, steps, slen) and (out.numel() == 0 or out.is_contiguous())
+    _lib.check(_lib.load().nm_align_softmax(_stream(), w.data_ptr(), steps, bsz, slen, out.data_ptr()),
+               "nm_align_softmax")
+    return out
+
+
 # ---- sentence-level heads (include/nmhip_pool.h, csrc/nm_pool.hip) ------------------------------------------------------
 POOL_MODES = {"max": 0, "avg": 1}
 

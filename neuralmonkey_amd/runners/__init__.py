@@ -6,3 +6,4 @@ from .tensor_runner import RepresentationRunner, TensorRunner                   
 from .label_runner import LabelRunner                                           # noqa: F401
 from .logits_runner import LogitsRunner                                         # noqa: F401
 from .regression_runner import RegressionRunner                                 # noqa: F401
+from .word_alignment_runner import WordAlignmentRunner                         # noqa: F401

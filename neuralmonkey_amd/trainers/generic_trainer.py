@@ -177,6 +177,13 @@ class GenericTrainer(GraphExecutor, Feedable):
             decoders.append(dec)
             scales.append(scale)
             counts.append(count)
+        # Supervised attention (decoders/word_alignment_decoder.py): such an objective is a term of its parent decoder's
+        # forward + backward, not a pass of its own -- it hangs itself on the parent's pass here and is visited after
+        # the parent below.  No such objective: ``order`` is the list as given.
+        order = sorted(range(len(decoders)), key=lambda i: hasattr(decoders[i], "attach"))
+        for dec, scale in zip(decoders, scales):
+            if hasattr(dec, "attach"):
+                dec.attach(ctx, scale, parent_trained=any(d is dec.decoder for d in decoders))
 
         terms = []
 
@@ -184,12 +191,13 @@ class GenericTrainer(GraphExecutor, Feedable):
             """Every objective's forward + backward; encoders shared by several decoders run their
             backward pass once, on the summed gradient (RunContext.defer_backward)."""
             ctx.memo["backward_deferred"] = True
-            results = []
+            results = [None] * len(decoders)
             del terms[:]
-            for dec, scale in zip(decoders, scales):
+            for i in order:
+                dec, scale = decoders[i], scales[i]
                 res = dec._train_loop(ctx, want_grad=True, grad_scale=scale)     # pylint: disable=protected-access
                 dec.backward(ctx, res)
-                results.append(res)
+                results[i] = res
             # ... then the self-critical and REINFORCE terms: each reuses the teacher-forced pass above where there is
             # one, and its tapes ADD to the flat gradient (the hand-scheduled backward above overwrites its slices)
             if critics:
