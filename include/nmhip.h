@@ -337,6 +337,17 @@ typedef struct nm_step_problem {
     const int32_t* add_ids; const int32_t* xc_ids;
 } nm_step_problem;
 int nm_step_group(void* stream, int64_t M, const nm_step_problem* problems, int32_t nproblems);
+/* Which kernel nm_step_group would launch for these descriptors (under the calling thread's context and the
+ * NM_STEP_DMA of the environment): one of the codes below, or < 0 with an error text for descriptors nm_step_group
+ * refuses.  The same function makes the choice for the launch.  Host only: nothing is launched. */
+#define NM_STEP_PLAN_16_1 0           /* step_group_kernel<16,1,0>: 16x16 tiles, M <= 256, at most 512 of them */
+#define NM_STEP_PLAN_16_2 1           /* step_group_kernel<16,2,0>: two row tiles per workgroup */
+#define NM_STEP_PLAN_16_1_PARTIALS 2  /* step_group_kernel<16,1,1>: a_kind 1 */
+#define NM_STEP_PLAN_MEDIUM_4_2_2 3   /* step_group_medium_kernel<4,2,2>: M > 256, at least 256 tiles of 64x64 */
+#define NM_STEP_PLAN_MEDIUM_8_1_1 4   /* step_group_medium_kernel<8,1,1>: M > 256, at most 640 tiles of 32x32 */
+#define NM_STEP_PLAN_MEDIUM_4_1_1 5   /* step_group_medium_kernel<4,1,1>: M > 256 otherwise */
+#define NM_STEP_PLAN_DMA 6            /* step_group_dma_kernel: NM_STEP_DMA=1, M > 256, every K a multiple of 64 */
+int nm_step_group_plan(int64_t M, const nm_step_problem* problems, int32_t nproblems);
 
 /* ---- COSTING ONLY (not called by the product path): C[M,N] = A[M,K] . B[N,K]^T with the fp32 operands emulated by
  * three bf16 matrix-core products (split-bf16: hi.hi + hi.lo + lo.hi, fp32 accumulate; terms = 1: plain bf16).  The

@@ -144,6 +144,7 @@ SIGNATURES = {
     "nm_attn_partials_layout": (I, [L, L, L, L, P, P, P]),
     "nm_attn_fwd_partials": (I, [P, P, P, P, P, P, P, L, L, L, L, L, P, L]),
     "nm_step_group": (I, [P, L, P, ctypes.c_int32]),
+    "nm_step_group_plan": (I, [L, P, ctypes.c_int32]),
     "nm_decoder_step_fused": (I, [P, P]),
     "nm_dec_step_cluster_supported": (I, [L, L, L, L]),
     "nm_dec_step_cluster_workspace_bytes": (L, [L, L]),

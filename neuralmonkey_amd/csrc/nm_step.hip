@@ -556,12 +556,44 @@ static bool sgd_switch() {            // (read per call: a test flips it within 
     return e && e[0] == '1';
 }
 
-extern "C" int nm_step_group(void* stream, int64_t M, const nm_step_problem* probs, int32_t nprob) {
+// Which kernel a group runs on and the tile geometry that goes with it.  nm_step_group launches what this says and
+// nm_step_group_plan reports it: ONE rule, so a test that asks which instance a shape reaches cannot drift from the launch.
+struct StepPlan {
+    int kernel;               // NM_STEP_PLAN_* (include/nmhip.h)
+    int tm, tile_n;           // 16-row tiles per workgroup row, columns per workgroup
+    int tiles_m, wblocks;
+};
+
+static int step_group_plan(int64_t M, const nm_step_problem* probs, int32_t nprob, StepPlan* plan) {
     NM_REQUIRE(probs && nprob >= 1 && nprob <= NM_STEP_MAX_PROB, "nm_step_group: 1..%d problems", NM_STEP_MAX_PROB);
     NM_REQUIRE(M > 0 && M < (1 << 24), "nm_step_group: bad M %ld", (long)M);
-    StepGroup g;
-    g.nprob = nprob;
-    g.M = (int)M;
+    for (int i = 0; i < nprob; ++i) {
+        const nm_step_problem& q = probs[i];
+        NM_REQUIRE(q.Bt && q.N > 0 && q.K > 0 && q.K % 16 == 0 && q.N < (1 << 24) && q.K < (1 << 24),
+                   "nm_step_group[%d]: bad shape N=%ld K=%ld (K must be a multiple of 16)", i, (long)q.N, (long)q.K);
+        NM_REQUIRE(nm_aligned16(q.Bt) && q.ldb % 4 == 0 && q.ldb >= q.K, "nm_step_group[%d]: weights must be [N,K], "
+                   "16-byte aligned rows", i);
+        NM_REQUIRE(q.a_kind == 0 || q.a_kind == 1, "nm_step_group[%d]: bad a_kind", i);
+        if (q.a_kind == 0)
+            NM_REQUIRE(q.A && nm_aligned16(q.A) && q.lda % 4 == 0 && q.lda >= q.K, "nm_step_group[%d]: A must be "
+                       "[M,K] with 16-byte aligned rows", i);
+        else
+            NM_REQUIRE(q.pctx && q.pstat && nm_aligned16(q.pctx) && nm_aligned16(q.pstat) && q.nchunk >= 1 &&
+                       q.nchunk <= NM_STEP_MAX_CHUNK && (!q.weights || (q.energies && q.S > 0 && q.mask_div >= 1 &&
+                                                                         q.mask_mod >= 1)),
+                       "nm_step_group[%d]: bad attention partials (1..%d chunks)", i, NM_STEP_MAX_CHUNK);
+        NM_REQUIRE(q.epilogue >= 0 && q.epilogue <= 2, "nm_step_group[%d]: bad epilogue", i);
+        if (q.epilogue == 0) NM_REQUIRE(q.C && q.ldc >= q.N && (!q.add || q.ldadd >= q.N) && (q.act == 0 || q.act == 1),
+                                        "nm_step_group[%d]: bad plain epilogue", i);
+        if (q.epilogue == 1) NM_REQUIRE(q.bias && q.ru && q.rh && q.h && q.N % 2 == 0 && q.ldh >= q.N / 2 &&
+                                            (!q.add || q.ldadd >= q.N), "nm_step_group[%d]: bad gates epilogue", i);
+        NM_REQUIRE((!q.add_ids || q.add) && (!q.xc_ids || q.epilogue == 2), "nm_step_group[%d]: row ids without the "
+                   "operand they index", i);
+        if (q.epilogue == 2) NM_REQUIRE(q.xc && q.ru && q.h && q.h_out && q.ldxc >= q.N && q.ldh >= q.N &&
+                                        q.ldho >= q.N && (!q.h_out2 || q.ldho2 >= q.N),
+                                        "nm_step_group[%d]: bad candidate epilogue", i);
+        NM_REQUIRE(q.a_kind == probs[0].a_kind, "nm_step_group: the problems of a group share one operand loader");
+    }
     // tile height: 16 rows per workgroup while the whole group stays within 512 workgroups (two per CU), else 32
     long tiles16 = 0;
     for (int i = 0; i < nprob; ++i) tiles16 += (long)nm_cdiv(M, 16) * nm_cdiv(probs[i].N, 16);
@@ -589,37 +621,45 @@ extern "C" int nm_step_group(void* stream, int64_t M, const nm_step_problem* pro
         for (int i = 0; i < nprob; ++i) t44 += (long)nm_cdiv(M, 64) * nm_cdiv(probs[i].N, 64);
         if (t44 >= 256) { tr = 2; tc = 2; }
     }
-    const int tm = medium ? 2 * tr : ((probs[0].a_kind == 0 && tiles16 > 512) ? 2 : 1);
-    const int tile_n = medium ? 32 * tc : 16;
-    g.tiles_m = nm_cdiv(M, 16 * tm);
-    g.wblocks = (probs[0].a_kind == 1 && probs[0].weights) ? nm_cdiv(M, 16) : 0;
+    plan->tm = medium ? 2 * tr : ((probs[0].a_kind == 0 && tiles16 > 512) ? 2 : 1);
+    plan->tile_n = medium ? 32 * tc : 16;
+    plan->tiles_m = nm_cdiv(M, 16 * plan->tm);
+    plan->wblocks = (probs[0].a_kind == 1 && probs[0].weights) ? nm_cdiv(M, 16) : 0;
+    long grid = plan->wblocks;
+    for (int i = 0; i < nprob; ++i) grid += (long)plan->tiles_m * nm_cdiv(probs[i].N, plan->tile_n);
+    // few tiles (a single 512-wide product at 640 rows: 320 tiles on 256 CUs): 8 waves split K, so that the one or
+    // two workgroups a CU gets are half as long
+    if (dma) plan->kernel = NM_STEP_PLAN_DMA;
+    else if (medium && tr == 2 && tc == 2) plan->kernel = NM_STEP_PLAN_MEDIUM_4_2_2;
+    else if (medium && grid <= 640) plan->kernel = NM_STEP_PLAN_MEDIUM_8_1_1;
+    else if (medium) plan->kernel = NM_STEP_PLAN_MEDIUM_4_1_1;
+    else if (probs[0].a_kind == 1) plan->kernel = NM_STEP_PLAN_16_1_PARTIALS;
+    else if (plan->tm == 2) plan->kernel = NM_STEP_PLAN_16_2;
+    else plan->kernel = NM_STEP_PLAN_16_1;
+    return NM_OK;
+}
+
+// The NM_STEP_PLAN_* code of the kernel nm_step_group would launch for these descriptors under the calling thread's
+// context and environment, negative (with an error text) for descriptors it would refuse.  Nothing is launched.
+extern "C" int nm_step_group_plan(int64_t M, const nm_step_problem* probs, int32_t nprob) {
+    StepPlan plan;
+    const int rc = step_group_plan(M, probs, nprob, &plan);
+    return rc != NM_OK ? rc : plan.kernel;
+}
+
+extern "C" int nm_step_group(void* stream, int64_t M, const nm_step_problem* probs, int32_t nprob) {
+    StepPlan plan;
+    const int rc = step_group_plan(M, probs, nprob, &plan);
+    if (rc != NM_OK) return rc;
+    StepGroup g;
+    g.nprob = nprob;
+    g.M = (int)M;
+    g.tiles_m = plan.tiles_m;
+    g.wblocks = plan.wblocks;
     int next = 0;
     for (int i = 0; i < nprob; ++i) {
         const nm_step_problem& q = probs[i];
         StepProb& p = g.p[i];
-        NM_REQUIRE(q.Bt && q.N > 0 && q.K > 0 && q.K % 16 == 0 && q.N < (1 << 24) && q.K < (1 << 24),
-                   "nm_step_group[%d]: bad shape N=%ld K=%ld (K must be a multiple of 16)", i, (long)q.N, (long)q.K);
-        NM_REQUIRE(nm_aligned16(q.Bt) && q.ldb % 4 == 0 && q.ldb >= q.K, "nm_step_group[%d]: weights must be [N,K], "
-                   "16-byte aligned rows", i);
-        NM_REQUIRE(q.a_kind == 0 || q.a_kind == 1, "nm_step_group[%d]: bad a_kind", i);
-        if (q.a_kind == 0)
-            NM_REQUIRE(q.A && nm_aligned16(q.A) && q.lda % 4 == 0 && q.lda >= q.K, "nm_step_group[%d]: A must be "
-                       "[M,K] with 16-byte aligned rows", i);
-        else
-            NM_REQUIRE(q.pctx && q.pstat && nm_aligned16(q.pctx) && nm_aligned16(q.pstat) && q.nchunk >= 1 &&
-                       q.nchunk <= NM_STEP_MAX_CHUNK && (!q.weights || (q.energies && q.S > 0 && q.mask_div >= 1 &&
-                                                                         q.mask_mod >= 1)),
-                       "nm_step_group[%d]: bad attention partials (1..%d chunks)", i, NM_STEP_MAX_CHUNK);
-        NM_REQUIRE(q.epilogue >= 0 && q.epilogue <= 2, "nm_step_group[%d]: bad epilogue", i);
-        if (q.epilogue == 0) NM_REQUIRE(q.C && q.ldc >= q.N && (!q.add || q.ldadd >= q.N) && (q.act == 0 || q.act == 1),
-                                        "nm_step_group[%d]: bad plain epilogue", i);
-        if (q.epilogue == 1) NM_REQUIRE(q.bias && q.ru && q.rh && q.h && q.N % 2 == 0 && q.ldh >= q.N / 2 &&
-                                            (!q.add || q.ldadd >= q.N), "nm_step_group[%d]: bad gates epilogue", i);
-        NM_REQUIRE((!q.add_ids || q.add) && (!q.xc_ids || q.epilogue == 2), "nm_step_group[%d]: row ids without the "
-                   "operand they index", i);
-        if (q.epilogue == 2) NM_REQUIRE(q.xc && q.ru && q.h && q.h_out && q.ldxc >= q.N && q.ldh >= q.N &&
-                                        q.ldho >= q.N && (!q.h_out2 || q.ldho2 >= q.N),
-                                        "nm_step_group[%d]: bad candidate epilogue", i);
         p.A = q.A; p.lda = q.lda; p.Bt = q.Bt; p.ldb = q.ldb; p.N = q.N; p.K = q.K;
         p.a_kind = q.a_kind; p.epilogue = q.epilogue; p.act = q.act; p.nchunk = q.nchunk;
         p.bias = q.bias; p.add = q.add; p.ldadd = q.ldadd; p.C = q.C; p.ldc = q.ldc;
@@ -629,26 +669,35 @@ extern "C" int nm_step_group(void* stream, int64_t M, const nm_step_problem* pro
         p.h_out = q.h_out; p.ldho = q.ldho; p.h_out2 = q.h_out2; p.ldho2 = q.ldho2;
         p.add_ids = q.add_ids; p.xc_ids = q.xc_ids;
         g.begin[i] = next;
-        next += g.tiles_m * nm_cdiv(q.N, tile_n);
+        next += g.tiles_m * nm_cdiv(q.N, plan.tile_n);
     }
     for (int i = nprob; i <= NM_STEP_MAX_PROB; ++i) g.begin[i] = next;
     for (int i = nprob; i < NM_STEP_MAX_PROB; ++i) g.p[i] = g.p[0];
-    for (int i = 1; i < nprob; ++i)
-        NM_REQUIRE(probs[i].a_kind == probs[0].a_kind, "nm_step_group: the problems of a group share one operand loader");
     hipStream_t st = nm_stream(stream);
     const unsigned grid = (unsigned)(next + g.wblocks);
-    // few tiles (a single 512-wide product at 640 rows: 320 tiles on 256 CUs): 8 waves split K, so that the one or
-    // two workgroups a CU gets are half as long
-    if (dma)
+    switch (plan.kernel) {
+    case NM_STEP_PLAN_DMA:
         hipLaunchKernelGGL(step_group_dma_kernel, dim3(grid), dim3(256), 8 * SGD_IMG * 4, st, g);
-    else if (medium && tr == 2 && tc == 2)
+        break;
+    case NM_STEP_PLAN_MEDIUM_4_2_2:
         hipLaunchKernelGGL((step_group_medium_kernel<4, 2, 2>), dim3(grid), dim3(1024), 0, st, g);
-    else if (medium && grid <= 640)
+        break;
+    case NM_STEP_PLAN_MEDIUM_8_1_1:
         hipLaunchKernelGGL((step_group_medium_kernel<8, 1, 1>), dim3(grid), dim3(512), 0, st, g);
-    else if (medium) hipLaunchKernelGGL((step_group_medium_kernel<4, 1, 1>), dim3(grid), dim3(256), 0, st, g);
-    else if (probs[0].a_kind == 1) hipLaunchKernelGGL((step_group_kernel<16, 1, 1>), dim3(grid), dim3(1024), 0, st, g);
-    else if (tm == 2) hipLaunchKernelGGL((step_group_kernel<16, 2, 0>), dim3(grid), dim3(1024), 0, st, g);
-    else hipLaunchKernelGGL((step_group_kernel<16, 1, 0>), dim3(grid), dim3(1024), 0, st, g);
+        break;
+    case NM_STEP_PLAN_MEDIUM_4_1_1:
+        hipLaunchKernelGGL((step_group_medium_kernel<4, 1, 1>), dim3(grid), dim3(256), 0, st, g);
+        break;
+    case NM_STEP_PLAN_16_1_PARTIALS:
+        hipLaunchKernelGGL((step_group_kernel<16, 1, 1>), dim3(grid), dim3(1024), 0, st, g);
+        break;
+    case NM_STEP_PLAN_16_2:
+        hipLaunchKernelGGL((step_group_kernel<16, 2, 0>), dim3(grid), dim3(1024), 0, st, g);
+        break;
+    default:
+        hipLaunchKernelGGL((step_group_kernel<16, 1, 0>), dim3(grid), dim3(1024), 0, st, g);
+        break;
+    }
     NM_LAUNCH_CHECK("nm_step_group");
 }
 

@@ -557,6 +557,18 @@ class StepGroup:
     def launch(self):
         _lib.check(self._fn(_stream(), self.rows, self.arr, len(self.arr)), "nm_step_group")
 
+    def plan(self):
+        """The kernel ``launch`` would run (a name of ``STEP_GROUP_PLANS``), chosen by the library's own rule;
+        descriptors ``launch`` would refuse raise the same error.  Nothing is launched."""
+        code = _lib.load().nm_step_group_plan(self.rows, self.arr, len(self.arr))
+        if code < 0:
+            _lib.check(code, "nm_step_group_plan")
+        return STEP_GROUP_PLANS[code]
+
+
+# the NM_STEP_PLAN_* codes of include/nmhip.h, in order
+STEP_GROUP_PLANS = ("16x1", "16x2", "16x1-partials", "medium-4x2x2", "medium-8x1x1", "medium-4x1x1", "dma")
+
 
 class DecoderStepCall:
     """``nm_decoder_step_fused``: the descriptor of a whole decoder step, built once from persistent buffers;

@@ -942,6 +942,8 @@ LEDGER = {
     "nm_attn_step_bwd": "tests/test_attn_bwd_gpu.py::test_attn_step_bwd_matches_float64_autograd via ops.attn_step_bwd",
     "nm_attn_fwd_partials": "tests/test_step_group_gpu.py::test_partials_merged_in_the_operand_loader via ops.attn_fwd_partials",
     "nm_step_group": "tests/test_step_group_gpu.py::test_plain_problems_share_a_launch via ops.StepGroup",
+    # (a shape query that launches nothing -- but a test calls it for every case of the sweep, so it names that test)
+    "nm_step_group_plan": "tests/test_step_group_sweep_gpu.py::test_sweep_case via ops.StepGroup",
     "nm_decoder_step_fused": "tests/test_step_group_gpu.py::test_decoder_step_fused_is_the_oracle_step via ops.DecoderStepCall",
     "nm_beam_backtrace": "tests/test_beam_fused_gpu.py::test_backtrace_equals_the_per_step_history_gather via ops.beam_backtrace",
     "nm_beam_topk_step_fused": BEAM + "test_step_against_float64 via ops.beam_topk_step_fused",
