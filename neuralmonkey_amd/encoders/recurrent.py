@@ -599,7 +599,9 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
         base = store.offset(names[0]) + d_in * 4 * h                         # rows d_in .. d_in + h: the state half
         stride = store.offset(names[1]) - store.offset(names[0]) if ndir == 2 else 0
         wh = store.theta.as_strided((ndir, h, 4 * h), (stride, 4 * h, 1), base)
-        if not gru.cluster_ok(ctx.session, bsz, h, ndir, wh, wh):
+        # the LSTM kernels' own shape query (their LDS need is not the GRU loops'), then what every cluster loop asks
+        # of its recurrent kernel: 16-byte aligned rows
+        if not ops.lstm_seq_supported(bsz, h, ndir) or not gru.cluster_ok(ctx.session, bsz, h, ndir, wh, wh):
             return None
         rev0 = spec.direction == "backward"
         width = ndir * h
@@ -659,14 +661,15 @@ class RecurrentEncoder(ModelPart, TemporalStatefulWithOutput):
         cells = self._cells[layer]
         ndir, h = len(cells), spec.size
         width = ndir * h
-        if os.environ.get("NM_NEMATUS_CLUSTER", "1") != "0":      # (read per call: tests compare both schedules)
-            fused = self._nematus_cluster_layer(tape, x, bsz, slen, lengths, layer)
-            if fused is None and os.environ.get("NM_LSTM_CLUSTER", "1") != "0":
-                fused = self._lstm_cluster_layer(tape, x, bsz, slen, lengths, layer)
-            if fused is None and os.environ.get("NM_GRU_LAYER_CLUSTER", "1") != "0":
-                fused = self._gru_cluster_layer(tape, x, bsz, slen, lengths, layer)
-            if fused is not None:
-                return fused
+        # one switch per cell type, each read on its own (and per call: tests compare both schedules): switching one
+        # cell's loops off leaves the other two where they are.  Each method returns None for another cell type.
+        for switch, cluster_layer in (("NM_NEMATUS_CLUSTER", self._nematus_cluster_layer),
+                                      ("NM_LSTM_CLUSTER", self._lstm_cluster_layer),
+                                      ("NM_GRU_LAYER_CLUSTER", self._gru_cluster_layer)):
+            if os.environ.get(switch, "1") != "0":
+                fused = cluster_layer(tape, x, bsz, slen, lengths, layer)
+                if fused is not None:
+                    return fused
         out = tape.new((bsz * slen, width))
         final = tape.new((bsz, width))
         for d, cell in enumerate(cells):

@@ -673,6 +673,17 @@ def embedding_scatter_add(dtable, ids, d, skip_pad=False):
 _LNB_WS = {}
 
 
+def _layer_norm_bwd_workspace(device, d):
+    """The [G][2][D] partial sums between nm_layer_norm_bwd_params' main kernel and its reduce launch, one buffer per
+    (device, width, stream, tag) like the column sums': two launches of one width on two streams must not share it."""
+    key = (device, d, _stream(), workspace_tag())
+    ws = _LNB_WS.get(key)
+    if ws is None:
+        ws = _LNB_WS[key] = torch.empty(_lib.load().nm_layer_norm_bwd_params_workspace_bytes(d) // 4,
+                                        dtype=torch.float32, device=device)
+    return ws
+
+
 def layer_norm_bwd_params(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, accumulate=True, accumulate_dx=False):
     """dx of a layer norm and its parameter gradients in one call (nm_layer_norm_bwd_params); ``accumulate_dx``: dx is
     added to what ``dx`` holds."""
@@ -680,11 +691,7 @@ def layer_norm_bwd_params(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, accumulat
     d = x.shape[-1]
     rows = x.numel() // d
     assert dy.is_contiguous() and x.is_contiguous() and dx.is_contiguous()
-    key = (x.device, d)
-    ws = _LNB_WS.get(key)
-    if ws is None:
-        ws = _LNB_WS[key] = torch.empty(lib.nm_layer_norm_bwd_params_workspace_bytes(d) // 4, dtype=torch.float32,
-                                        device=x.device)
+    ws = _layer_norm_bwd_workspace(x.device, d)
     _lib.check(lib.nm_layer_norm_bwd_params(_stream(), dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                             gamma.data_ptr(), dx.data_ptr(), rows, d, dgamma.data_ptr(),
                                             dbeta.data_ptr(), int(bool(accumulate)) | (2 if accumulate_dx else 0),
@@ -1298,6 +1305,13 @@ def gru_seq_bwd(steps, ndir, rows, hsz, dh, dout, dout_strides, ru0, ru_step, c0
 
 def lstm_seq_workspace_floats(rows, hsz, ndir) -> int:
     return _lib.load().nm_lstm_seq_workspace_bytes(rows, hsz, ndir) // 4
+
+
+def lstm_seq_supported(rows, hsz, ndir) -> bool:
+    """Do the LSTM loops take this shape as one cluster launch each (nm_lstm_seq_fwd / nm_lstm_seq_bwd)?  The LSTM
+    kernels' own answer: for a shape they do not take their workspace is the bare header (what no shape at all gets)."""
+    lib = _lib.load()
+    return lib.nm_lstm_seq_workspace_bytes(rows, hsz, ndir) > lib.nm_lstm_seq_workspace_bytes(0, 0, 0)
 
 
 def lstm_seq_fwd(steps, ndir, rows, hsz, xp, x_strides, h_in0, h_out0, h_step, gates0, g_step, c0, c_step, wh, workspace,

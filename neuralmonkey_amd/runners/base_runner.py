@@ -65,18 +65,22 @@ class LazyLosses(dict):
     def _fill(self) -> None:
         pending, self._pending = self._pending, None
         if pending is not None:
-            values = [float(x) for x in pending.get()]
-            # one value more than there are names: the session's device error word of that step (Session.error_word).
+            from ..runtime import error_flag_set
+            raw = pending.get()
+            values = [float(x) for x in raw]
+            # one value more than there are names: the session's device error word of that step (Session.error_word),
+            # as raw int32 bits -- read as such (runtime.error_flag_set), never as a float.
             # Set = a GRU time loop of the step gave up and its update was skipped on the device: the session runs the
             # step (and those enqueued since) again on the per-step path and these losses become that run's
-            if len(values) > len(self._names) and values[len(self._names)] != 0.0:
+            if len(values) > len(self._names) and error_flag_set(raw):
                 sess = getattr(pending, "session", None)
                 if sess is None:
                     raise RuntimeError("the training step that produced these losses ran a GRU time loop that gave up "
                                        "waiting for a hand-off between workgroups: its results are garbage")
                 sess.recover_training(pending=pending)
-                values = [float(x) for x in pending.get()]
-                if values[len(self._names)] != 0.0:
+                raw = pending.get()
+                values = [float(x) for x in raw]
+                if error_flag_set(raw):
                     sess.raise_device_error()
             dict.update(self, zip(self._names, values))
 

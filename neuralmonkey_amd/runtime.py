@@ -250,6 +250,19 @@ def _to_host(val):
     return out
 
 
+def error_flag_set(values) -> bool:
+    """Is the device error word that travels behind a training step's losses set?  ``values``: the float32 array a
+    step's ``HostPending`` hands out; its LAST slot holds the raw int32 bits of ``Session.error_word`` (a 1 there is
+    the denormal 1.4e-45 when read as a float).  The slot is read through an integer view: a float comparison -- or
+    a conversion to a Python float -- sees zero once the process flushes denormals (torch.set_flush_denormal, a
+    library built with -ffast-math that sets FTZ/DAZ on load), and a give-up nobody notices voids every later
+    update (the word is sticky) without an error."""
+    last = np.ascontiguousarray(np.asarray(values).reshape(-1)[-1:])
+    if last.dtype.itemsize != 4:
+        raise TypeError("the error flag travels as one 32-bit word, got {}".format(last.dtype))
+    return int(last.view(np.int32)[0]) != 0
+
+
 class HostPending:
     """A few device words on their way to the host: an asynchronous copy into pinned memory plus an event.
     ``get()`` waits for the event.  A training step hands its loss scalars back like this, so the host thread is
@@ -536,6 +549,11 @@ class Session:
         warnings.warn("a GRU time loop launched as one cluster kernel gave up waiting for a hand-off between "
                       "workgroups (something else held compute units for 0.2 s): the affected work is run again and "
                       "this session continues with two launches per recurrent step (what NM_CLUSTER_LOOPS=0 selects)")
+        self._forget_given_up_work()
+
+    def _forget_given_up_work(self) -> None:
+        """Clear the error word and drop everything that may hold a given-up loop's launch or results."""
+        torch.cuda.synchronize(self.device)
         if self._error_word is not None:
             self._error_word.zero_()
         self._error_pending = None
@@ -559,11 +577,11 @@ class Session:
         if not getattr(self, "_recovering", False):
             while len(guard) > lookback:
                 rec = guard[0]
-                if rec["pending"] is not None and float(rec["pending"].get().reshape(-1)[-1]) != 0.0:
+                if rec["pending"] is not None and error_flag_set(rec["pending"].get()):
                     self.recover_training(0)
                     break
                 guard.pop(0)
-        guard.append({"trainer": trainer, "feed": dict(feed), "pending": None,
+        guard.append({"trainer": trainer, "feed": dict(feed), "pending": None, "clustered": self.use_cluster_loops,
                       "snap": (self.global_step, [(t, t.snapshot_counters(self)) for t in self._guarded_trainers])})
 
     def settle_training(self) -> None:
@@ -574,7 +592,7 @@ class Session:
         if self.device.type != "cuda" or getattr(self, "_recovering", False):
             return
         for i, rec in enumerate(list(guard)):
-            if rec["pending"] is not None and float(rec["pending"].get().reshape(-1)[-1]) != 0.0:
+            if rec["pending"] is not None and error_flag_set(rec["pending"].get()):
                 self.recover_training(i)
                 self.settle_training()              # (the steps that were run again left records of their own)
                 return
@@ -605,12 +623,23 @@ class Session:
         # earlier records may have failed too (the word is sticky, but a step can finish before anybody looks)
         for i in range(index):
             rec = guard[i]
-            if rec["pending"] is not None and float(rec["pending"].get().reshape(-1)[-1]) != 0.0:
+            if rec["pending"] is not None and error_flag_set(rec["pending"].get()):
                 index = i
                 break
         bad = guard[index:]
         del guard[index:]
-        self.demote_cluster_loops()
+        if self.use_cluster_loops or not bad[0].get("clustered", True):
+            # (a step that was enqueued with the loops off already and set the word all the same: the fallback's own
+            # failure -- demote_cluster_loops raises)
+            self.demote_cluster_loops()
+        else:
+            # the step ran cluster loops, but somebody who saw the sticky word first has switched them off since (a
+            # caller that drives inference on this session by hand between a training step and the read of its flag;
+            # TensorFlowManager.execute calls settle_training first, so it never gets here).  The failed step's update
+            # was skipped on the device all the same, so the steps are run again; only a word set by the re-run
+            # itself is an error (below).  Steps enqueued after that caller cleared the word were applied: settle
+            # before such a pass.
+            self._forget_given_up_work()
         step, counters = bad[0]["snap"]
         self.global_step = step
         for trainer, snap in counters:
@@ -624,6 +653,8 @@ class Session:
                     rec["pending"].redirect(new)
         finally:
             self._recovering = False
+        if self.cluster_failure():                 # the per-step path has nothing to wait for: its own failure
+            self.raise_device_error()
 
     def poll_device_errors(self, last: bool = False) -> None:
         """Kept for callers that drive a session without TensorFlowManager.execute: raise if the error word is set."""

@@ -125,6 +125,14 @@ class TensorFlowManager:
         NEXT with the same runners: its encoder side (what ``GraphExecutor.ahead_fetches`` lists: encoder states,
         attention keys, initial decoder states) is evaluated on a second stream while this batch decodes -- both
         are latency-bound and leave most CUs idle (runtime.Session.run).  Inference with one session only."""
+        if not train:
+            # validation or inference between training steps: the error flags of the steps enqueued so far are read
+            # first (and a step whose time loop gave up is run again), before anything is launched.  Otherwise the
+            # check below would take the training step's sticky word for this batch's, clear it, and the steps whose
+            # updates it voided would never be run again.  Nothing outstanding: no cost; otherwise a wait for steps
+            # this batch would queue behind anyway.
+            for sess in self.sessions:
+                sess.settle_training()
         default_feed_dict = _feed_dicts(batch, feedables, train=train)
         executables = [runner.get_executable(compute_losses=compute_losses, summaries=summaries,
                                              num_sessions=len(self.sessions)) for runner in runners]

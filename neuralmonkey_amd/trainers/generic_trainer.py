@@ -337,7 +337,8 @@ class GenericTrainer(GraphExecutor, Feedable):
         # (behind them travels the session's device error word: a time loop that gave up makes the step garbage)
         if DEFER_LOSSES and all(isinstance(v, torch.Tensor) and v.is_cuda for v in values):
             # (gathered with 4-byte device copies into one of four persistent slots; the error word travels as its
-            # raw int32 bits: zero stays 0.0, one reads as a denormal -- the host only asks "is it zero")
+            # raw int32 bits in the last slot.  As a float a set word is the denormal 1.4e-45, which a host that
+            # flushes denormals reads as 0.0: the host reads the slot back as an integer, runtime.error_flag_set)
             sess = ctx.session
             vals = ctx.buffer((id(self), "loss_vals", sess.global_step % 4), (len(values) + 1,))
             for i, v in enumerate(values):

@@ -12,6 +12,12 @@ results are garbage.  That must cost a slow step, not the run:
     embedding_scatter_kernel) and no two runs add them in the same order.  A skipped, doubled or garbage update
     would move every variable by ~learning rate = 1e-4; the tests allow a mean difference of 2e-8.
 
+What runs between the given-up step and the read of its flag must not break that: a validation pass
+(TensorFlowManager.execute(train=False) settles the training steps before it launches anything), a save
+(Session.settle_training), an open accumulation window, another optimizer, a host that flushes denormals (the flag
+travels as int32 bits in a float32 slot and is read as an integer) -- and the Nematus, LSTM and GRU-layer loops of the
+taped path raise the same word as the fast path's.
+
 The give-up is forced by the library's test hook (nm_gru_seq_force_give_up: the launch raises its error word at
 once instead of after 0.2 s) and, once, provoked for real: 32 workgroups of another stream sit on 32 CUs with all
 their LDS while a training step is launched.  Reference semantics: trainers/generic_trainer.py:179-195 (one update
@@ -74,28 +80,47 @@ def _uses_cluster_loops(model):
     return model.tf_manager.sessions[0].use_cluster_loops and ops.gru_seq_supported(BATCH, DIM, 1)
 
 
-def _train(model, batches, fail_before=None, stepwise_from=None, read_losses="end"):
+def _same_slots(sess, ref_sess):
+    """The optimizer's slots (Adam: m, v; Momentum: its accumulator) are the reference's: a garbage gradient that got
+    through the gate would be in them for good."""
+    slots, ref_slots = sess.store.slots(), ref_sess.store.slots()
+    assert len(slots) == len(ref_slots) and slots
+    for got, want in zip(slots, ref_slots):
+        assert torch.isfinite(got).all()
+        assert float((got - want).abs().max()) <= 1e-4 * float(want.abs().max()), \
+            "optimizer slots differ: a garbage update got through"
+
+
+def _train(model, batches, fail_before=None, stepwise_from=None, read_losses="end", between=None):
     """Training steps over ``batches``; ``fail_before`` = index of the step whose first cluster loop is forced to
     give up; ``stepwise_from`` = index from which the session is put on the per-step path by hand (the reference
-    run); ``read_losses``: "each" reads every step's losses right away, "end" only after the last step."""
+    run); ``read_losses``: "each" reads every step's losses right away, "end" only after the last step, "later"
+    not at all: the unread results are returned in place of the losses; ``between(i)`` runs after step ``i`` was
+    enqueued (and, with "each", read)."""
     from neuralmonkey_amd import ops
     tfm = model.tf_manager
     sess = tfm.sessions[0]
     results = []
-    for i, ds in enumerate(batches):
-        if stepwise_from is not None and i == stepwise_from:
-            torch.cuda.synchronize()
-            sess.use_cluster_loops = False
-            sess._graphs.clear()                                   # pylint: disable=protected-access
-        if fail_before is not None and i == fail_before:
-            ops.gru_seq_force_give_up(1)
-        res = tfm.execute(ds, model.trainer.feedables, [model.trainer], train=True)[0]
-        if read_losses == "each":
-            dict(res.losses)
-        results.append(res)
-    losses = [dict(r.losses) for r in results]
-    torch.cuda.synchronize()
-    assert ops.gru_seq_force_give_up(0) == 0, "the forced give-up was never consumed: no cluster loop was launched"
+    try:
+        for i, ds in enumerate(batches):
+            if stepwise_from is not None and i == stepwise_from:
+                torch.cuda.synchronize()
+                sess.use_cluster_loops = False
+                sess._graphs.clear()                                   # pylint: disable=protected-access
+            if fail_before is not None and i == fail_before:
+                ops.gru_seq_force_give_up(1)
+            res = tfm.execute(ds, model.trainer.feedables, [model.trainer], train=True)[0]
+            if read_losses == "each":
+                dict(res.losses)
+            results.append(res)
+            if between is not None:
+                between(i)
+        losses = results if read_losses == "later" else [dict(r.losses) for r in results]
+        torch.cuda.synchronize()
+        left = ops.gru_seq_force_give_up(0)
+    finally:
+        ops.gru_seq_force_give_up(0)
+    assert left == 0, "the forced give-up was never consumed: no cluster loop was launched"
     return losses, sess.store.theta.clone(), sess
 
 
@@ -118,11 +143,8 @@ def test_a_given_up_time_loop_costs_a_slow_step_not_the_run(dev, fail_at, read_l
     _close(losses, ref_losses, exact_at=fail_at if fail_at == 0 else None)
     _same_variables(theta, ref_theta)
     assert not sess.cluster_failure()
-    m, v = sess.store.ensure_adam()
-    rm, rv = ref_sess.store.ensure_adam()
-    assert torch.isfinite(m).all() and torch.isfinite(v).all()
-    assert float((m - rm).abs().max()) <= 1e-4 * float(rm.abs().max()), "optimizer slots differ: a garbage update got through"
-    assert float((v - rv).abs().max()) <= 1e-4 * float(rv.abs().max())
+    assert len(sess.store.slots()) == 2          # Adam's m and v
+    _same_slots(sess, ref_sess)
 
 
 def test_the_garbage_update_is_skipped_on_the_device(dev):
@@ -266,3 +288,245 @@ def test_a_real_compute_unit_hog_makes_the_loop_give_up_and_the_step_is_recovere
     assert len([w for w in caught if "gave up waiting" in str(w.message)]) == 1
     _close(losses, ref_losses)
     _same_variables(sess.store.theta, ref_theta)
+
+
+# ---- training, validation, logging: what runs between a given-up step and the read of its losses ---------------------
+def _validation_after(model, step, ds, seen):
+    """A ``between`` hook for ``_train``: after training step ``step`` the greedy runner decodes ``ds`` twice in a row
+    (train=False), the decoded tokens go to ``seen``."""
+    tfm = model.tf_manager
+
+    def between(i):
+        if i == step:
+            for _ in range(2):
+                res = tfm.execute(ds, model.greedy_runner.feedables, [model.greedy_runner], train=False)[0]
+                seen.append(res.outputs["target"])
+    return between
+
+
+def _recovered_and_reference(dev, build, batches, fail_at, validate_after, read_losses="end"):
+    """The reference run (per-step path by hand from ``fail_at``) and the run whose step ``fail_at`` gives up, both
+    with the same validation batch decoded after step ``validate_after``.  -> (losses, theta, sess, warnings told,
+    decoded) of the recovered run and (losses, theta, sess) of the reference."""
+    val = _batches(len(batches) + 1)[-1]
+    ref_model = build()
+    if not _uses_cluster_loops(ref_model):
+        pytest.skip("cluster loops are off or unsupported on this device")
+    ref = _train(ref_model, batches, stepwise_from=fail_at, read_losses=read_losses,
+                 between=_validation_after(ref_model, validate_after, val, []))
+    model = build()
+    seen = []
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        got = _train(model, batches, fail_before=fail_at, read_losses=read_losses,
+                     between=_validation_after(model, validate_after, val, seen))
+    told = [w for w in caught if "gave up waiting" in str(w.message)]
+    return got + (told, seen), ref
+
+
+@pytest.mark.parametrize("fail_at,validate_after", [(0, 0), (2, 2), (1, 2)])
+def test_a_validation_pass_before_the_losses_are_read_does_not_break_recovery(dev, fail_at, validate_after):
+    """Train, validate, log: TensorFlowManager.execute(train=False) runs while the given-up step's error flag is still
+    unread.  It must settle the training steps first -- not take their sticky word for its own batch's, clear it and
+    leave the voided updates missing (the loss read then met a session that was demoted already and raised)."""
+    (losses, theta, sess, told, seen), (ref_losses, ref_theta, ref_sess) = _recovered_and_reference(
+        dev, lambda: _model(dev), _batches(5), fail_at, validate_after)
+    assert len(told) == 1, "exactly one warning"
+    assert not sess.use_cluster_loops and sess.cluster_demotions == 1
+    assert sess.global_step == ref_sess.global_step == 5
+    _close(losses, ref_losses)
+    _same_variables(theta, ref_theta)
+    _same_slots(sess, ref_sess)
+    assert not sess.cluster_failure()
+    # the same variables, both runs on the per-step path, no atomics in the forward pass
+    assert len(seen) == 2 and seen[0] == seen[1]
+
+
+def test_delayed_updates_survive_a_validation_pass_inside_the_window(dev):
+    """As above with an accumulation window open: the failed batch's gradient was zeroed on the device, the validation
+    pass settles the window before it runs and the window goes on from the batch that is run again."""
+    from neuralmonkey_amd.trainers import DelayedUpdateTrainer
+    (losses, theta, sess, told, _), (ref_losses, ref_theta, _) = _recovered_and_reference(
+        dev, lambda: _model(dev, DelayedUpdateTrainer, batches_per_update=3), _batches(6), 1, 1)
+    _close(losses, ref_losses)
+    _same_variables(theta, ref_theta)
+    assert sess.global_step == 2 and not sess.use_cluster_loops and len(told) == 1
+
+
+def test_momentum_recovers_through_a_validation_pass_like_adam(dev):
+    """The (2, 2) case with tf.train.MomentumOptimizer: one slot, no bias-correction counter.  The update is
+    lr * (momentum-averaged clipped gradient) instead of Adam's ~lr per element, so the test first checks that ONE
+    update moves the variables by far more than ``_same_variables`` allows two runs to differ."""
+    from neuralmonkey_amd.optimizers import MomentumOptimizer
+    from neuralmonkey_amd.trainers import GenericTrainer
+    build = lambda: _model(dev, GenericTrainer, optimizer=MomentumOptimizer(learning_rate=0.1, momentum=0.9))
+    start = build().tf_manager.sessions[0].store.theta.clone()
+    (losses, theta, sess, told, seen), (ref_losses, ref_theta, ref_sess) = _recovered_and_reference(
+        dev, build, _batches(5), 2, 2)
+    moved = float((ref_theta - start).abs().mean()) / 5
+    print("one Momentum update moves the variables by {:.3g} on average".format(moved))
+    assert moved > 100 * 2e-8, "a lost update would hide inside the bound of _same_variables: raise the learning rate"
+    assert len(told) == 1 and sess.cluster_demotions == 1 and not sess.use_cluster_loops
+    assert sess.global_step == ref_sess.global_step == 5
+    _close(losses, ref_losses)
+    _same_variables(theta, ref_theta)
+    assert len(sess.store.slots()) == 1          # the accumulator
+    _same_slots(sess, ref_sess)
+    assert not sess.cluster_failure()
+    assert len(seen) == 2 and seen[0] == seen[1]
+
+
+def test_saving_settles_the_outstanding_steps_first(dev, tmp_path):
+    """TensorFlowManager.save -> Session.settle_training: with the last step's flag unread, saving runs that step
+    again first.  The file holds the variables of three clean steps and step 3; the losses read afterwards are the
+    re-run's (HostPending.redirect)."""
+    batches = _batches(3)
+    ref_model = _model(dev)
+    if not _uses_cluster_loops(ref_model):
+        pytest.skip("cluster loops are off or unsupported on this device")
+    ref_losses, ref_theta, _ = _train(ref_model, batches, stepwise_from=2)
+    model = _model(dev)
+    path = str(tmp_path / "variables")
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        results, _, sess = _train(model, batches, fail_before=2, read_losses="later")
+        model.tf_manager.save(path)
+        torch.cuda.synchronize()
+        assert sess.global_step == 3
+        assert sess.__dict__.get("_train_guard") == [], "every outstanding record was read"
+        assert not sess.use_cluster_loops and sess.cluster_demotions == 1
+        saved = sess.store.theta.clone()
+        losses = [dict(r.losses) for r in results]
+    assert len([w for w in caught if "gave up waiting" in str(w.message)]) == 1
+    _same_variables(saved, ref_theta)
+    assert torch.equal(sess.store.theta, saved), "reading the losses after the save changed nothing"
+    _close(losses, ref_losses)
+    fresh = _model(dev)
+    fresh.tf_manager.restore(path)
+    fresh_sess = fresh.tf_manager.sessions[0]
+    assert torch.equal(fresh_sess.store.theta, saved) and fresh_sess.global_step == 3
+
+
+def test_recovery_tolerates_a_session_that_was_demoted_already(dev):
+    """A caller that drives inference on the session by hand sees the last training step's sticky word first and
+    switches the loops off (what TensorFlowManager.execute did before it settled the training steps).  The read of
+    the step's losses still runs the step again: ``recover_training`` raises only when the re-run sets the word."""
+    batches = _batches(3)
+    ref_model = _model(dev)
+    if not _uses_cluster_loops(ref_model):
+        pytest.skip("cluster loops are off or unsupported on this device")
+    ref_losses, ref_theta, ref_sess = _train(ref_model, batches, stepwise_from=2)
+    model = _model(dev)
+    sess = model.tf_manager.sessions[0]
+
+    def by_hand(i):
+        if i == 2:
+            assert sess.cluster_failure()
+            sess.demote_cluster_loops()
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        losses, theta, _ = _train(model, batches, fail_before=2, between=by_hand)
+    assert len([w for w in caught if "gave up waiting" in str(w.message)]) == 1
+    assert not sess.use_cluster_loops and sess.cluster_demotions == 1 and sess.global_step == 3
+    _close(losses, ref_losses)
+    _same_variables(theta, ref_theta)
+    _same_slots(sess, ref_sess)
+    assert not sess.cluster_failure()
+
+
+def test_recovery_with_the_host_flushing_denormals(dev):
+    """The error word travels behind the losses as raw int32 bits in a float32 slot: a 1 is the denormal 1.4e-45, which
+    a host with flush-to-zero on reads as 0.0.  Read through an integer view (runtime.error_flag_set) the give-up is
+    seen all the same; before, no warning came and the sticky word voided every later update."""
+    batches = _batches(5)
+    ref_model = _model(dev)
+    if not _uses_cluster_loops(ref_model):
+        pytest.skip("cluster loops are off or unsupported on this device")
+    ref_losses, ref_theta, ref_sess = _train(ref_model, batches, stepwise_from=2)
+    model = _model(dev)
+    if not torch.set_flush_denormal(True):
+        pytest.skip("this host cannot flush denormals")
+    try:
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            losses, theta, sess = _train(model, batches, fail_before=2)
+    finally:
+        torch.set_flush_denormal(False)
+    told = [w for w in caught if "gave up waiting" in str(w.message)]
+    assert len(told) == 1, "exactly one warning"
+    assert not sess.use_cluster_loops and sess.cluster_demotions == 1
+    assert sess.global_step == ref_sess.global_step == len(batches)
+    _close(losses, ref_losses)
+    _same_variables(theta, ref_theta)
+    assert not sess.cluster_failure()
+    assert len(sess.store.slots()) == 2
+    _same_slots(sess, ref_sess)
+
+
+# ---- the other loops that raise the same word: NematusGRU, LSTM and GRU layers of the taped path ---------------------
+def _taped_config(cell):
+    from oracle import general_ref as G
+    if cell == "NematusGRU":
+        return G.Config(rnn_layers=((256, "bidirectional", "NematusGRU"),), dec_cell="NematusGRU", conditional_gru=True,
+                        rnn_size=8, output_projection=("nematus", "tanh", 1.0)), "nematus_seq_fwd"
+    if cell == "LSTM":
+        return G.Config(rnn_layers=((256, "bidirectional", "LSTM"),), dec_cell="LSTM", rnn_size=8), "lstm_seq_fwd"
+    # (layer-normed: the general path, encoders/recurrent.py::_gru_cluster_layer)
+    return G.Config(rnn_layers=((256, "bidirectional", "GRU"),), add_layer_norm=True, dec_cell="GRU",
+                    rnn_size=8), "gru_seq_fwd"
+
+
+@pytest.mark.parametrize("cell", ["NematusGRU", "LSTM", "GRU"])
+def test_the_taped_path_loops_recover_like_the_fast_path(dev, cell, monkeypatch):
+    """encoders/recurrent.py: the Nematus, LSTM and GRU-layer loops raise the session's word like the fast path's.
+    Three Adam steps (lr 1e-4) on a 256-wide, 5-sentence model, step 1's first loop -- the encoder layer's -- gives up.
+
+    Reference: the same model on the per-step path from the start.  A lost or doubled update moves every trained
+    element by about lr; the float atomics' order moves them by orders of magnitude less.  The test checks that
+    premise itself: two per-step runs differ by less than lr / 10000 on average; the recovered run must be within
+    lr / 100 of the reference."""
+    import types
+    from neuralmonkey_amd import ops
+    from tests.test_general_gpu import _build, _data
+    cfg, loop = _taped_config(cell)
+    lr = 1e-4
+    batches = [_data(5, 7, 6, 8, seed=3 + i)[0] for i in range(3)]
+    calls = []                                       # (training step, demotions so far) of every forward loop
+    now = {"step": 0, "sess": None}
+    real = getattr(ops, loop)
+
+    def spy(*a, **k):
+        calls.append((now["step"], getattr(now["sess"], "cluster_demotions", 0)))
+        return real(*a, **k)
+    monkeypatch.setattr(ops, loop, spy)
+
+    def run(**how):
+        m = _build(dev, cfg, 12, 8, init_std=0.08)
+        assert type(m["trainer"].optimizer).__name__ == "AdamOptimizer" and m["trainer"].optimizer.learning_rate(1) == lr
+        model = types.SimpleNamespace(tf_manager=m["tfm"], trainer=m["trainer"])
+        now["step"], now["sess"] = 0, m["tfm"].sessions[0]
+        del calls[:]
+
+        def between(i):
+            now["step"] = i + 1
+        return _train(model, batches, read_losses="each", between=between, **how)
+
+    ref_losses, ref_theta, _ = run(stepwise_from=0)
+    assert not calls, "the reference runs no cluster loop"
+    _, ref_theta2, _ = run(stepwise_from=0)
+    noise = float((ref_theta2 - ref_theta).abs().mean())
+    print("{}: two per-step runs differ by {:.3g} on average".format(cell, noise))
+    assert noise < lr / 10000
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        losses, theta, sess = run(fail_before=1)
+    assert len([w for w in caught if "gave up waiting" in str(w.message)]) == 1
+    assert not sess.use_cluster_loops and sess.cluster_demotions == 1 and sess.global_step == 3
+    steps = {step for step, _ in calls}
+    assert 0 in steps and 1 in steps, "the layer took its loop before the failure"
+    assert 2 not in steps and all(demoted == 0 for _, demoted in calls), "no loop after the failure"
+    _close(losses, ref_losses)
+    assert torch.isfinite(theta).all()
+    diff = float((theta - ref_theta).abs().mean())
+    print("{}: recovered run and reference differ by {:.3g} on average".format(cell, diff))
+    assert diff < lr / 100, "variables differ: an update was lost, doubled or garbage"

@@ -368,3 +368,62 @@ def test_stacked_gru_layers_of_the_general_path_take_the_loops(dev, monkeypatch)
             if err > 1e-3:
                 bad[name] = err
         assert not bad, "mode {}: {}".format(mode, bad)
+
+
+def _one_layer_config(cell):
+    from oracle import general_ref as G
+    if cell == "NematusGRU":
+        return G.Config(rnn_layers=((256, "bidirectional", "NematusGRU"),), dec_cell="NematusGRU", conditional_gru=True,
+                        rnn_size=8, output_projection=("nematus", "tanh", 1.0))
+    if cell == "LSTM":
+        return G.Config(rnn_layers=((256, "bidirectional", "LSTM"),), dec_cell="LSTM", rnn_size=8)
+    return G.Config(rnn_layers=((256, "bidirectional", "GRU"),), add_layer_norm=True, dec_cell="GRU", rnn_size=8)
+
+
+# cell type -> (its own switch, the forward and backward loop of ops its encoder layer launches)
+_LOOPS = {"NematusGRU": ("NM_NEMATUS_CLUSTER", "nematus_seq_fwd", "nematus_seq_bwd"),
+          "LSTM": ("NM_LSTM_CLUSTER", "lstm_seq_fwd", "lstm_seq_bwd"),
+          "GRU": ("NM_GRU_LAYER_CLUSTER", "gru_seq_fwd", "gru_seq_bwd")}
+
+
+@pytest.mark.parametrize("cell", sorted(_LOOPS))
+@pytest.mark.parametrize("switch", sorted(v[0] for v in _LOOPS.values()))
+def test_each_cell_types_switch_turns_off_its_own_loops_only(dev, cell, switch, monkeypatch):
+    """NM_NEMATUS_CLUSTER, NM_LSTM_CLUSTER and NM_GRU_LAYER_CLUSTER are read independently
+    (encoders/recurrent.py::_general_layer): a 256-wide bidirectional encoder layer of each cell type launches its
+    forward and backward loop once per training step unless ITS switch is 0 (NM_NEMATUS_CLUSTER=0 used to switch all
+    three off).  The GRU decoder's own loop is one direction wide: the encoder layer's is the launch with ndir = 2."""
+    from neuralmonkey_amd import ops
+    from tests.test_general_gpu import _build, _data
+    own, fwd, bwd = _LOOPS[cell]
+    calls = {"fwd": 0, "bwd": 0}
+
+    def spy(name, real):
+        def call(steps, ndir, *a, **k):
+            if ndir == 2:
+                calls[name] += 1
+            return real(steps, ndir, *a, **k)
+        return call
+    monkeypatch.setattr(ops, fwd, spy("fwd", getattr(ops, fwd)))
+    monkeypatch.setattr(ops, bwd, spy("bwd", getattr(ops, bwd)))
+    for name in (v[0] for v in _LOOPS.values()):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv(switch, "0")
+    m = _build(dev, _one_layer_config(cell), 12, 8, init_std=0.08)
+    assert m["tfm"].sessions[0].use_cluster_loops and ops.gru_seq_supported(5, 256, 2)
+    ds, _, _ = _data(5, 7, 6, 8)
+    res = m["tfm"].execute(ds, m["trainer"].feedables, [m["trainer"]], train=True)[0]
+    assert all(np.isfinite(v) for v in res.losses.values())
+    want = 0 if switch == own else 1
+    assert calls == {"fwd": want, "bwd": want}, (cell, switch, calls)
+
+
+def test_the_lstm_layer_asks_the_lstm_kernels_for_their_shapes(dev):
+    """ops.lstm_seq_supported is the LSTM loops' own query (the size of their workspace: the bare header for a shape
+    they do not take), the gate of encoders/recurrent.py::_lstm_cluster_layer."""
+    from neuralmonkey_amd import ops
+    for rows, h, ndir in [(5, 256, 2), (40, 512, 1), (33, 512, 2), (128, 512, 2), (9, 384, 1)]:
+        assert ops.lstm_seq_supported(rows, h, ndir)
+        assert ops.lstm_seq_workspace_floats(rows, h, ndir) * 4 > 256
+    for rows, h, ndir in [(5, 100, 2), (5, 640, 1), (5, 128, 1), (0, 256, 1), (5, 256, 3), (100000, 512, 2)]:
+        assert not ops.lstm_seq_supported(rows, h, ndir)
