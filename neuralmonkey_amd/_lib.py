@@ -253,6 +253,13 @@ ALIGN_SIGNATURES = {
     "nm_align_softmax": (I, [P, P, L, L, L, P]),
 }
 
+# ... and every symbol include/nmhip_speech.h declares (the speech front end: framing, FFT, mel filters, DCT and deltas of
+# SpeechFeaturesPreprocessor, csrc/nm_speech.hip)
+SPEECH_SIGNATURES = {
+    "nm_speech_frames": (I, [P, P, P, P, L, L, L, L, L, L, F, P, P, P, P, L, P, L, P, I, I, P, L]),
+    "nm_speech_deltas": (I, [P, P, L, P, L, L, L, L, L]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -325,7 +332,7 @@ def load():
                               + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
                               + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
                               + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
-                              + list(ALIGN_SIGNATURES.items())):
+                              + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -224,6 +224,11 @@ def _expand(patterns: Union[str, List[str]]) -> List[str]:
 _MAIN_BATCH_SIZE: List[Any] = []
 
 
+# chunk limits of a series-level preprocessor with a ``many`` method (``load``): items, and samples of their ``.data``
+MANY_ITEMS = 64
+MANY_SAMPLES = 1 << 24
+
+
 def load(name: str, series: List[str], data: List[Any], batching: BatchingScheme = None,
          outputs: List[Tuple] = None, buffer_size: int = None, shuffled: bool = False) -> Dataset:
     """dataset.py:207-333.  A series is given by one of
@@ -265,7 +270,24 @@ def load(name: str, series: List[str], data: List[Any], batching: BatchingScheme
         return lambda: reader(files)
 
     def mapped(preprocessor: Callable, source: str) -> Callable[[], Iterator]:
-        return lambda: (preprocessor(item) for item in factories[source]())
+        many = getattr(preprocessor, "many", None)
+        if not callable(many):
+            return lambda: (preprocessor(item) for item in factories[source]())
+
+        # a preprocessor that takes lists (processors.speech: one pair of launches per list) gets the series in chunks
+        # of MANY_ITEMS items or MANY_SAMPLES samples, whichever fills first; same items, same order, still lazy
+        def in_chunks() -> Iterator:
+            pending: List[Any] = []
+            weight = 0
+            for item in factories[source]():
+                pending.append(item)
+                weight += int(getattr(getattr(item, "data", None), "size", 1))
+                if len(pending) >= MANY_ITEMS or weight >= MANY_SAMPLES:
+                    yield from many(pending)
+                    pending, weight = [], 0
+            if pending:
+                yield from many(pending)
+        return in_chunks
     for sid, spec in zip(series, data):
         if isinstance(spec, (str, list)):
             factories[sid] = reading(plain_text_reader, _expand(spec))

@@ -1844,6 +1844,55 @@ def align_softmax(w, out):
     return out
 
 
+# ---- the speech front end (include/nmhip_speech.h, csrc/nm_speech.hip) --------------------------------------------------
+def _offsets(t, what):
+    assert t.dtype == torch.int64 and t.is_cuda and t.dim() == 1 and t.numel() >= 2 and t.is_contiguous(), what
+    return t.numel() - 1
+
+
+def speech_frames(wav, sample_off, frame_off, frame_len, frame_step, nfft, preemph, tables, mode, numcep, append_energy,
+                  out):
+    """Feature block 0 of a ragged batch of utterances: ``wav`` holds their fp32 samples back to back, utterance u at
+    ``sample_off[u] .. sample_off[u+1]``, its frames are the rows ``frame_off[u] .. frame_off[u+1]`` of ``out``
+    [total_frames, ld].  ``tables``: the device tensors of ``processors.speech.SpeechTables.on_device``."""
+    _f32(wav)
+    _f32(out)
+    count = _offsets(sample_off, "speech_frames sample_off")
+    assert _offsets(frame_off, "speech_frames frame_off") == count
+    assert wav.dim() == 1 and wav.is_contiguous() and out.dim() == 2 and (out.numel() == 0 or out.stride(1) == 1)
+    nbins = nfft // 2 + 1
+    bank, window, twiddles, ranges = tables["bank"], tables["window"], tables["twiddles"], tables["bank_range"]
+    nfilt = bank.shape[0]
+    assert _f32(bank).is_contiguous() and tuple(bank.shape) == (nfilt, nbins), tuple(bank.shape)
+    assert _f32(window).is_contiguous() and window.numel() == frame_len
+    assert _f32(twiddles).is_contiguous() and tuple(twiddles.shape) == (nfft // 2, 2)
+    assert _i32(ranges).is_contiguous() and tuple(ranges.shape) == (nfilt, 2)
+    dct, freqs = tables.get("dct"), tables.get("centroid_freqs")
+    if dct is not None:
+        assert _f32(dct).is_contiguous() and tuple(dct.shape) == (numcep, nfilt), tuple(dct.shape)
+    if freqs is not None:
+        assert _f32(freqs).is_contiguous() and freqs.numel() == nbins
+    ld = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+    _lib.check(_lib.load().nm_speech_frames(_stream(), wav.data_ptr(), sample_off.data_ptr(), frame_off.data_ptr(), count,
+                                            wav.numel(), out.shape[0], int(frame_len), int(frame_step), int(nfft),
+                                            float(preemph), window.data_ptr(), twiddles.data_ptr(), bank.data_ptr(),
+                                            ranges.data_ptr(), nfilt, _p(dct), int(numcep), _p(freqs), int(mode),
+                                            int(bool(append_energy)), out.data_ptr(), ld), "nm_speech_frames")
+    return out
+
+
+def speech_deltas(out, frame_off, width, order, window):
+    """One order of deltas: column block ``order + 1`` of ``out`` from block ``order`` (blocks ``width`` wide), rows
+    clamped to their own utterance."""
+    _f32(out)
+    count = _offsets(frame_off, "speech_deltas frame_off")
+    assert out.dim() == 2 and (out.numel() == 0 or out.stride(1) == 1)
+    ld = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+    _lib.check(_lib.load().nm_speech_deltas(_stream(), out.data_ptr(), ld, frame_off.data_ptr(), count, out.shape[0],
+                                            int(width), int(order), int(window)), "nm_speech_deltas")
+    return out
+
+
 # ---- sentence-level heads (include/nmhip_pool.h, csrc/nm_pool.hip) ------------------------------------------------------
 POOL_MODES = {"max": 0, "avg": 1}
 
