@@ -260,6 +260,14 @@ SPEECH_SIGNATURES = {
     "nm_speech_deltas": (I, [P, P, L, P, L, L, L, L, L]),
 }
 
+# ... and every symbol include/nmhip_imgread.h declares (the image reader's device pipeline: Pillow's convert, resize and
+# crop with the reference's zero padding, csrc/nm_imgread.hip)
+IMGREAD_SIGNATURES = {
+    "nm_imgread_rows": (I, [P, P, L, P, P, L, P, L, P, L, I, L, L, P, L]),
+    "nm_imgread_cols": (I, [P, P, L, P, P, L, P, L, P, L, I, L, L, P, ctypes.c_double, P, L]),
+    "nm_imgread_check": (I, [P, P, L, I, L, L]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -332,7 +340,8 @@ def load():
                               + list(REWARD_SIGNATURES.items()) + list(RL_SIGNATURES.items())
                               + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
                               + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
-                              + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())):
+                              + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
+                              + list(IMGREAD_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

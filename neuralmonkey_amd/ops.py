@@ -1893,6 +1893,63 @@ def speech_deltas(out, frame_off, width, order, window):
     return out
 
 
+# ---- the image reader's device pipeline (include/nmhip_imgread.h, csrc/nm_imgread.hip) ----------------------------------
+IMGREAD_TARGETS = {"L": 0, "RGB": 1, "F": 2}
+IMGREAD_OFFS, IMGREAD_GEOM = 6, 16
+
+
+def _imgread_chunk(offs, geom, bounds, coef, target):
+    """Checks the device arrays of one chunk (``readers.image_reader.ChunkPlan.arrays``); -> number of images."""
+    assert offs.dtype == torch.int64 and offs.is_cuda and offs.is_contiguous() and offs.dim() == 2, "imgread offs"
+    assert offs.shape[0] == IMGREAD_OFFS and offs.shape[1] >= 2, tuple(offs.shape)
+    count = offs.shape[1] - 1
+    assert _i32(geom).is_contiguous() and tuple(geom.shape) == (count, IMGREAD_GEOM), tuple(geom.shape)
+    assert _i32(bounds).is_contiguous() and bounds.dim() == 2 and bounds.shape[1] == 2, tuple(bounds.shape)
+    want = torch.float64 if target == IMGREAD_TARGETS["F"] else torch.int32
+    assert coef.dtype == want and coef.is_cuda and coef.dim() == 1 and coef.is_contiguous(), (coef.dtype, want)
+    return count
+
+
+def imgread_rows(src, offs, geom, bounds, coef, target, pad_w, max_rows, scratch):
+    """Horizontal pass of a chunk of decoded 8-bit images, the conversion to ``target`` folded into the loads: ``src``
+    (uint8, the images back to back) -> ``scratch`` (uint8 for the targets L and RGB, float32 for F)."""
+    count = _imgread_chunk(offs, geom, bounds, coef, target)
+    assert src.dtype == torch.uint8 and src.is_cuda and src.dim() == 1 and src.is_contiguous()
+    want = torch.float32 if target == IMGREAD_TARGETS["F"] else torch.uint8
+    assert scratch.dtype == want and scratch.is_cuda and scratch.dim() == 1 and scratch.is_contiguous()
+    _lib.check(_lib.load().nm_imgread_rows(_stream(), src.data_ptr(), src.numel(), offs.data_ptr(), geom.data_ptr(), count,
+                                           bounds.data_ptr(), bounds.shape[0], coef.data_ptr(), coef.numel(), int(target),
+                                           int(pad_w), int(max_rows), scratch.data_ptr(), scratch.numel()),
+               "nm_imgread_rows")
+    return scratch
+
+
+def imgread_cols(scratch, offs, geom, bounds, coef, target, out, sub=None, divide=1.0):
+    """Vertical pass, crop, zero padding and the optional ``(v - sub[c]) / divide`` epilogue: ``scratch`` -> ``out``
+    [N, pad_h, pad_w, C] float32 (rows contiguous; images and rows may be strided alike)."""
+    count = _imgread_chunk(offs, geom, bounds, coef, target)
+    _f32(out)
+    assert out.dim() == 4 and out.shape[0] == count and out.is_contiguous(), tuple(out.shape)
+    channels = 3 if target == IMGREAD_TARGETS["RGB"] else 1
+    assert out.shape[3] == channels, (tuple(out.shape), channels)
+    if sub is not None:
+        assert sub.dtype == torch.float64 and sub.is_cuda and sub.numel() == channels and sub.is_contiguous()
+    _lib.check(_lib.load().nm_imgread_cols(_stream(), scratch.data_ptr(), scratch.numel(), offs.data_ptr(),
+                                           geom.data_ptr(), count, bounds.data_ptr(), bounds.shape[0], coef.data_ptr(),
+                                           coef.numel(), int(target), out.shape[2], out.shape[1], _p(sub), float(divide),
+                                           out.data_ptr(), out.shape[2] * channels), "nm_imgread_cols")
+    return out
+
+
+def imgread_check(offs, geom, target, pad_w, pad_h):
+    """The host copies (NumPy) of a chunk's offsets and geometry, checked before they are uploaded."""
+    import numpy as np
+    assert offs.dtype == np.int64 and offs.flags.c_contiguous and offs.ndim == 2 and offs.shape[0] == IMGREAD_OFFS
+    assert geom.dtype == np.int32 and geom.flags.c_contiguous and geom.shape == (offs.shape[1] - 1, IMGREAD_GEOM)
+    _lib.check(_lib.load().nm_imgread_check(offs.ctypes.data, geom.ctypes.data, geom.shape[0], int(target), int(pad_w),
+                                            int(pad_h)), "nm_imgread_check")
+
+
 # ---- sentence-level heads (include/nmhip_pool.h, csrc/nm_pool.hip) ------------------------------------------------------
 POOL_MODES = {"max": 0, "avg": 1}
 
