@@ -1,4 +1,4 @@
-/* libnmhip -- C ABI of the optimizer family beyond Adam and Adadelta (csrc/nm_optim_family.hip), a companion of nmhip.h
+/* libnmhip -- C ABI of the optimizer family beyond Adam and Adadelta (csrc/nm_optim.hip), a companion of nmhip.h
  * with the same conventions: every function returns 0 on success, <0 on error with the text in nm_last_error(); tensor
  * pointers are DEVICE pointers owned by the caller (fp32 / int32 / int64 tables); `stream` is a hipStream_t passed as
  * void*; sizes are int64_t element counts.  Arguments are checked before anything is launched.  No kernel here uses
@@ -7,8 +7,8 @@
  * Reference: trainers/generic_trainer.py:64 takes any tf.train.Optimizer; these are TF 1.12's ApplyGradientDescent,
  * ApplyMomentum, ApplyAdagrad and ApplyRMSProp (core/kernels/training_ops.cc) as pass 3 of the flat optimizer: the chunk
  * and segment tables, the workspace (nm_optim_workspace_bytes) and the squared gradient norms in it are those of
- * nm_optim_partials / nm_optim_segments in nmhip.h, which run first.  Kinds 0 (Adam) and 1 (Adadelta) stay with
- * nm_optim_apply. */
+ * nm_optim_partials / nm_optim_segments in nmhip.h, which run first.  One kernel template serves all six kinds; kinds 0
+ * (Adam) and 1 (Adadelta) are launched through nm_optim_apply, which keeps its own argument checks. */
 #ifndef NMHIP_OPTIM_H
 #define NMHIP_OPTIM_H
 #include <stdint.h>

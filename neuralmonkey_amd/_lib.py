@@ -240,7 +240,7 @@ BNSYNC_SIGNATURES = {
 }
 
 # ... and every symbol include/nmhip_optim.h declares (the clip + update pass of GradientDescent, Momentum, Adagrad and
-# RMSProp, csrc/nm_optim_family.hip); the argument lists are nm_optim_apply's and nm_optim_apply_list's
+# RMSProp, csrc/nm_optim.hip); the argument lists are nm_optim_apply's and nm_optim_apply_list's
 OPTIM_SIGNATURES = {
     "nm_optim_update": (I, [P, I, P, P, P, P, P, P, P, P, P, P, L, L, F, F, F, F, F, L, L, P, P, L]),
     "nm_optim_update_list": (I, [P, I, P, P, P, P, P, P, P, P, P, P, L, L, F, F, F, F, F, P, L, P, P, L]),

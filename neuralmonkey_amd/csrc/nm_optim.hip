@@ -5,11 +5,14 @@
 //   per-tensor tf.clip_by_norm: g * c / max(||g||, c)              (:179-186)
 //   Adam (tf.train.AdamOptimizer, :55-57): lr_t = lr*sqrt(1-b2^t)/(1-b1^t)
 //   Adadelta (tf.train.AdadeltaOptimizer, tests/bpe.ini:102-108): TF 1.12 ApplyAdadelta
+//   GradientDescent, Momentum, Adagrad, RMSProp: TF 1.12's ApplyGradientDescent, ApplyMomentum, ApplyAdagrad and
+//   ApplyRMSProp (:64 takes any tf.train.Optimizer)
 // All variables live in one flat buffer (variables.py); a host-built chunk
 // table maps fixed-size chunks to variables ("segments") so that three launches
 // cover every tensor and all reductions have a fixed order (deterministic).
 #include "nm_common.h"
 #include "../../include/nmhip.h"
+#include "../../include/nmhip_optim.h"
 
 struct OptChunks {
     const long* chunk_start;   // [nchunk] flat offset
@@ -24,7 +27,7 @@ struct OptChunks {
 // pass 1: regulariser terms + squared gradient norm partials per chunk
 __global__ __launch_bounds__(256) void opt_reg_sumsq_kernel(OptChunks t, const float* __restrict__ theta,
                                                             float* __restrict__ grad, float l1w, float l2w,
-                                                            float* __restrict__ partial, int c0,
+                                                            float* __restrict__ partial, int vec, int c0,
                                                             const int* __restrict__ list) {
     __shared__ float sh[3][4];
     const int c = list ? list[blockIdx.x] : c0 + (int)blockIdx.x;     // (list: the chunks a rank owns, in any order)
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(256) void opt_reg_sumsq_kernel(OptChunks t, const f
         return g;
     };
     int done = 0;
-    if ((base & 3) == 0) {                 // 16-byte rows: the pass is a pure stream over theta and grad
+    if (vec && (base & 3) == 0) {          // 16-byte rows (vec: of 16-byte buffers): a pure stream over theta and grad
         const int len4 = len >> 2;
         const float4* th4 = reinterpret_cast<const float4*>(theta + base);
         float4* g4 = reinterpret_cast<float4*>(grad + base);
@@ -96,13 +99,65 @@ __global__ void opt_seg_reduce_kernel(OptChunks t, const float* __restrict__ par
     }
 }
 
-// pass 3: clip per tensor + Adam
-__global__ __launch_bounds__(256) void opt_adam_kernel(OptChunks t, float* __restrict__ theta,
-                                                       const float* __restrict__ grad,
-                                                       float* __restrict__ m, float* __restrict__ v,
-                                                       const float* __restrict__ seg_norm2, float clip,
-                                                       float lr_t, float b1, float b2, float eps, int c0,
-                                                       const int* __restrict__ skip, const int* __restrict__ list) {
+// pass 3: clip per tensor + the update of one kind.  A kind touches only the streams it has:
+// (kinds 0 and 1 come in through nm_optim_apply, nmhip.h; 2..5 through nm_optim_update, nmhip_optim.h)
+//   0 Adam             theta, g, m, v        -> theta, m, v           m, v EMA; var -= lr_t*m/(sqrt(v) + eps)
+//   1 Adadelta         theta, g, accum, au   -> theta, accum, au      accum = rho*accum + (1-rho)*g^2;
+//                                                                     upd = sqrt(au + eps)*rsqrt(accum + eps)*g;
+//                                                                     var -= lr*upd; au = rho*au + (1-rho)*upd^2
+//                                                                     (the order TF's kernel evaluates them in)
+//   2 GradientDescent  theta, g              -> theta                 var -= lr*g
+//   3 Momentum         theta, g, accum       -> theta, accum          accum = accum*mu + g; var -= lr*accum
+//                                                                     (Nesterov: var -= g*lr + accum*mu*lr)
+//   4 Adagrad          theta, g, accum       -> theta, accum          accum += g*g; var -= g*lr*rsqrt(accum)
+//   5 RMSProp          theta, g, ms, mom     -> theta, ms, mom        ms += (g*g - ms)*(1-decay);
+//                                                                     mom = mom*mu + (g*lr)/sqrt(ms + eps); var -= mom
+#define OPT_ADAM 0
+#define OPT_ADADELTA 1
+__host__ __device__ constexpr bool opt_has0(int kind) { return kind != NM_OPTIM_SGD; }
+__host__ __device__ constexpr bool opt_has1(int kind) { return kind <= OPT_ADADELTA || kind == NM_OPTIM_RMSPROP; }
+
+// one element of kind KIND: th, a, b are updated in place (a, b: the slots the kind has)
+template <int KIND>
+__device__ __forceinline__ void opt_one(float& th, float g, float& a, float& b, float p0, float p1, float p2,
+                                        float p3) {
+    if (KIND == OPT_ADAM) {                                 // p0 lr_t, p1 beta1, p2 beta2, p3 epsilon; a = m, b = v
+        const float mm = p1 * a + (1.0f - p1) * g;
+        const float vv = p2 * b + (1.0f - p2) * g * g;
+        a = mm;
+        b = vv;
+        th -= p0 * mm / (sqrtf(vv) + p3);
+    } else if (KIND == OPT_ADADELTA) {                      // p0 lr, p1 rho, p2 epsilon; a = accum, b = accum_update
+        const float acc = p1 * a + (1.0f - p1) * g * g;
+        const float au = b;
+        const float upd = sqrtf(au + p2) * (1.0f / sqrtf(acc + p2)) * g;
+        a = acc;
+        th -= p0 * upd;
+        b = p1 * au + (1.0f - p1) * upd * upd;
+    } else if (KIND == NM_OPTIM_SGD) {
+        th -= p0 * g;
+    } else if (KIND == NM_OPTIM_MOMENTUM) {                 // p0 lr, p1 momentum, p2 != 0: Nesterov
+        a = a * p1 + g;
+        if (p2 != 0.0f) th -= g * p0 + a * p1 * p0;
+        else th -= p0 * a;
+    } else if (KIND == NM_OPTIM_ADAGRAD) {                  // p0 lr
+        a += g * g;
+        th -= g * p0 * (1.0f / sqrtf(a));
+    } else {                                                // RMSProp: p0 lr, p1 decay, p2 momentum, p3 epsilon
+        a += (g * g - a) * (1.0f - p1);
+        b = b * p2 + (g * p0) / sqrtf(a + p3);
+        th -= b;
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void opt_update_kernel(OptChunks t, float* __restrict__ theta,
+                                                         const float* __restrict__ grad, float* __restrict__ s0,
+                                                         float* __restrict__ s1, const float* __restrict__ seg_norm2,
+                                                         float clip, float p0, float p1, float p2, float p3, int vec,
+                                                         int c0, const int* __restrict__ skip,
+                                                         const int* __restrict__ list) {
+    constexpr bool HAS0 = opt_has0(KIND), HAS1 = opt_has1(KIND);
     if (skip && *skip != 0) return;          // the step's gradient is garbage (a time loop gave up): nothing is applied
     const int c = list ? list[blockIdx.x] : c0 + (int)blockIdx.x;
     const int seg = t.chunk_seg[c];
@@ -111,40 +166,38 @@ __global__ __launch_bounds__(256) void opt_adam_kernel(OptChunks t, float* __res
     const int len = t.chunk_len[c];
     float scale = 1.0f;
     if (clip > 0.0f) scale = clip / fmaxf(sqrtf(seg_norm2[seg]), clip);
-    for (int i = threadIdx.x; i < len; i += 256) {
-        const float g = grad[base + i] * scale;
-        const float mm = b1 * m[base + i] + (1.0f - b1) * g;
-        const float vv = b2 * v[base + i] + (1.0f - b2) * g * g;
-        m[base + i] = mm;
-        v[base + i] = vv;
-        theta[base + i] -= lr_t * mm / (sqrtf(vv) + eps);
+    int done = 0;
+    // 16-byte rows: every variable starts on one, a shard's cut may not; vec: the kind's buffers start on one too
+    if (vec && (base & 3) == 0) {
+        const int len4 = len >> 2;
+        float4* th4 = reinterpret_cast<float4*>(theta + base);
+        const float4* g4 = reinterpret_cast<const float4*>(grad + base);
+        float4* a4 = HAS0 ? reinterpret_cast<float4*>(s0 + base) : nullptr;
+        float4* b4 = HAS1 ? reinterpret_cast<float4*>(s1 + base) : nullptr;
+        for (int i = threadIdx.x; i < len4; i += 256) {
+            float4 th = th4[i];
+            const float4 g = g4[i];
+            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+            if (HAS0) a = a4[i];
+            if (HAS1) b = b4[i];
+            opt_one<KIND>(th.x, g.x * scale, a.x, b.x, p0, p1, p2, p3);
+            opt_one<KIND>(th.y, g.y * scale, a.y, b.y, p0, p1, p2, p3);
+            opt_one<KIND>(th.z, g.z * scale, a.z, b.z, p0, p1, p2, p3);
+            opt_one<KIND>(th.w, g.w * scale, a.w, b.w, p0, p1, p2, p3);
+            if (HAS0) a4[i] = a;
+            if (HAS1) b4[i] = b;
+            th4[i] = th;
+        }
+        done = len4 << 2;
     }
-}
-
-// pass 3, Adadelta: accum <- rho*accum + (1-rho)*g^2; update = sqrt(accum_update + eps) * rsqrt(accum + eps) * g;
-// var -= lr*update; accum_update <- rho*accum_update + (1-rho)*update^2   (the order TF's kernel evaluates them in)
-__global__ __launch_bounds__(256) void opt_adadelta_kernel(OptChunks t, float* __restrict__ theta,
-                                                           const float* __restrict__ grad,
-                                                           float* __restrict__ accum, float* __restrict__ accum_update,
-                                                           const float* __restrict__ seg_norm2, float clip,
-                                                           float lr, float rho, float eps, int c0,
-                                                           const int* __restrict__ skip, const int* __restrict__ list) {
-    if (skip && *skip != 0) return;
-    const int c = list ? list[blockIdx.x] : c0 + (int)blockIdx.x;
-    const int seg = t.chunk_seg[c];
-    if (!(t.seg_flags[seg] & 2)) return;
-    const long base = t.chunk_start[c];
-    const int len = t.chunk_len[c];
-    float scale = 1.0f;
-    if (clip > 0.0f) scale = clip / fmaxf(sqrtf(seg_norm2[seg]), clip);
-    for (int i = threadIdx.x; i < len; i += 256) {
-        const float g = grad[base + i] * scale;
-        const float a = rho * accum[base + i] + (1.0f - rho) * g * g;
-        const float au = accum_update[base + i];
-        const float upd = sqrtf(au + eps) * (1.0f / sqrtf(a + eps)) * g;
-        accum[base + i] = a;
-        theta[base + i] -= lr * upd;
-        accum_update[base + i] = rho * au + (1.0f - rho) * upd * upd;
+    for (int i = done + threadIdx.x; i < len; i += 256) {
+        float th = theta[base + i], a = 0.0f, b = 0.0f;
+        if (HAS0) a = s0[base + i];
+        if (HAS1) b = s1[base + i];
+        opt_one<KIND>(th, grad[base + i] * scale, a, b, p0, p1, p2, p3);
+        if (HAS0) s0[base + i] = a;
+        if (HAS1) s1[base + i] = b;
+        theta[base + i] = th;
     }
 }
 
@@ -157,9 +210,43 @@ static OptChunks make_chunks(const int64_t* chunk_start, const int32_t* chunk_le
     t.seg_flags = seg_flags; t.nchunk = (int)nchunk; t.nseg = (int)nseg;
     return t;
 }
+static bool has_tables(const OptChunks& t) {
+    return t.chunk_start && t.chunk_len && t.chunk_seg && t.seg_first && t.seg_count && t.seg_flags;
+}
 
 // workspace: partial[nchunk*3] + seg_norm2[nseg]  (floats)
 extern "C" int64_t nm_optim_workspace_bytes(int64_t nchunk, int64_t nseg) { return (nchunk * 3 + nseg) * 4; }
+
+// The chunks of one launch of pass 1 or 3: the range [a, b) of the table, or (by_list) a device array of b chunk
+// indices.  ``*grid``: how many (0: nothing to launch).
+static int opt_select(const char* who, bool by_list, int64_t a, int64_t b, const int32_t* list, int64_t nchunk,
+                      unsigned* grid) {
+    if (by_list)
+        NM_REQUIRE(b >= 0 && b <= nchunk && (b == 0 || list), "%s: bad chunk list (%ld of %ld)", who, (long)b,
+                   (long)nchunk);
+    else
+        NM_REQUIRE(a >= 0 && a <= b && b <= nchunk, "%s: bad chunk range [%ld, %ld) of %ld", who, (long)a, (long)b,
+                   (long)nchunk);
+    *grid = (unsigned)(by_list ? b : b - a);
+    return NM_OK;
+}
+
+// pass 1 behind nm_optim_partials (a range: the list-less case) and nm_optim_partials_list
+static int opt_partials(const char* who, bool by_list, void* stream, const float* theta, float* grad, OptChunks t,
+                        int64_t nchunk, int64_t nseg, float l1_weight, float l2_weight, int64_t a, int64_t b,
+                        const int32_t* list, void* workspace, int64_t workspace_bytes) {
+    NM_REQUIRE(theta && grad && has_tables(t) && workspace, "%s: null pointer", who);
+    NM_REQUIRE(nchunk > 0 && nseg > 0 && workspace_bytes >= nm_optim_workspace_bytes(nchunk, nseg), "%s: bad sizes",
+               who);
+    unsigned grid;
+    const int rc = opt_select(who, by_list, a, b, list, nchunk, &grid);
+    if (rc != NM_OK || grid == 0) return rc;
+    const int vec = nm_aligned16(theta) && nm_aligned16(grad);      // the kernel's float4 rows need 16-byte buffers
+    hipLaunchKernelGGL(opt_reg_sumsq_kernel, dim3(grid), dim3(256), 0, nm_stream(stream), t, theta, grad, l1_weight,
+                       l2_weight, reinterpret_cast<float*>(workspace), vec, by_list ? 0 : (int)a,
+                       by_list ? list : nullptr);
+    NM_LAUNCH_CHECK(who);
+}
 
 // pass 1 over the chunks [chunk_begin, chunk_end): regulariser terms into the gradient, the chunks' partial sums into
 // the workspace.  A rank that owns a slice of the flat buffers (sharded optimizer, distributed.py) runs its own chunks
@@ -171,18 +258,10 @@ extern "C" int nm_optim_partials(void* stream, const float* theta, float* grad, 
                                  const int32_t* seg_count, const int32_t* seg_flags, int64_t nchunk, int64_t nseg,
                                  float l1_weight, float l2_weight, int64_t chunk_begin, int64_t chunk_end,
                                  void* workspace, int64_t workspace_bytes) {
-    NM_REQUIRE(theta && grad && chunk_start && chunk_len && chunk_seg && seg_first && seg_count && seg_flags && workspace,
-               "nm_optim_partials: null pointer");
-    NM_REQUIRE(nchunk > 0 && nseg > 0 && workspace_bytes >= nm_optim_workspace_bytes(nchunk, nseg),
-               "nm_optim_partials: bad sizes");
-    NM_REQUIRE(chunk_begin >= 0 && chunk_begin <= chunk_end && chunk_end <= nchunk,
-               "nm_optim_partials: bad chunk range [%ld, %ld) of %ld", (long)chunk_begin, (long)chunk_end, (long)nchunk);
-    if (chunk_begin == chunk_end) return NM_OK;
-    OptChunks t = make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg);
-    hipLaunchKernelGGL(opt_reg_sumsq_kernel, dim3((unsigned)(chunk_end - chunk_begin)), dim3(256), 0, nm_stream(stream),
-                       t, theta, grad, l1_weight, l2_weight, reinterpret_cast<float*>(workspace), (int)chunk_begin,
-                       (const int*)nullptr);
-    NM_LAUNCH_CHECK("nm_optim_partials");
+    return opt_partials("nm_optim_partials", false, stream, theta, grad,
+                        make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg),
+                        nchunk, nseg, l1_weight, l2_weight, chunk_begin, chunk_end, nullptr, workspace,
+                        workspace_bytes);
 }
 
 // The same over a LIST of chunks (a device array of ``count`` chunk indices): everything a rank of the sharded optimizer
@@ -194,17 +273,9 @@ extern "C" int nm_optim_partials_list(void* stream, const float* theta, float* g
                                       const int32_t* seg_count, const int32_t* seg_flags, int64_t nchunk, int64_t nseg,
                                       float l1_weight, float l2_weight, const int32_t* chunk_list, int64_t count,
                                       void* workspace, int64_t workspace_bytes) {
-    NM_REQUIRE(theta && grad && chunk_start && chunk_len && chunk_seg && seg_first && seg_count && seg_flags && workspace,
-               "nm_optim_partials_list: null pointer");
-    NM_REQUIRE(nchunk > 0 && nseg > 0 && workspace_bytes >= nm_optim_workspace_bytes(nchunk, nseg),
-               "nm_optim_partials_list: bad sizes");
-    NM_REQUIRE(count >= 0 && count <= nchunk && (count == 0 || chunk_list), "nm_optim_partials_list: bad chunk list (%ld of %ld)",
-               (long)count, (long)nchunk);
-    if (count == 0) return NM_OK;
-    OptChunks t = make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg);
-    hipLaunchKernelGGL(opt_reg_sumsq_kernel, dim3((unsigned)count), dim3(256), 0, nm_stream(stream), t, theta, grad,
-                       l1_weight, l2_weight, reinterpret_cast<float*>(workspace), 0, chunk_list);
-    NM_LAUNCH_CHECK("nm_optim_partials_list");
+    return opt_partials("nm_optim_partials_list", true, stream, theta, grad,
+                        make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg),
+                        nchunk, nseg, l1_weight, l2_weight, 0, count, chunk_list, workspace, workspace_bytes);
 }
 
 // pass 2: per-variable squared gradient norms and the global L1 / L2 terms from the partial vector, in a fixed order
@@ -223,6 +294,70 @@ extern "C" int nm_optim_segments(void* stream, const int64_t* chunk_start, const
     NM_LAUNCH_CHECK("nm_optim_segments");
 }
 
+// A pass-3 entry point: its name, the kinds it takes and how it words its refusals.  The two pairs differ, and callers
+// read the texts and codes: nm_optim_apply* (nmhip.h) wants both slots and answers "null pointer" / "bad sizes";
+// nm_optim_update* (nmhip_optim.h, ``itemised``) wants the slots its kind has, names what is missing, checks the
+// tables and answers a short workspace with NM_ERR_WORKSPACE.
+struct OptEntry {
+    const char* who;
+    int kind_lo, kind_hi;
+    const char* kinds;
+    bool itemised, by_list;
+};
+#define OPT_KINDS_APPLY "0 Adam, 1 Adadelta"
+#define OPT_KINDS_UPDATE "2 GradientDescent, 3 Momentum, 4 Adagrad, 5 RMSProp"
+static const OptEntry OPT_APPLY = {"nm_optim_apply", OPT_ADAM, OPT_ADADELTA, OPT_KINDS_APPLY, false, false};
+static const OptEntry OPT_APPLY_LIST = {"nm_optim_apply_list", OPT_ADAM, OPT_ADADELTA, OPT_KINDS_APPLY, false, true};
+static const OptEntry OPT_UPDATE = {"nm_optim_update", NM_OPTIM_SGD, NM_OPTIM_RMSPROP, OPT_KINDS_UPDATE, true, false};
+static const OptEntry OPT_UPDATE_LIST = {"nm_optim_update_list", NM_OPTIM_SGD, NM_OPTIM_RMSPROP, OPT_KINDS_UPDATE, true,
+                                         true};
+
+// everything a pass-3 entry point refuses before it looks at its chunks
+static int opt_check(const OptEntry& e, int32_t kind, const float* theta, const float* grad, const float* slot0,
+                     const float* slot1, const OptChunks& t, int64_t nchunk, int64_t nseg, const void* workspace,
+                     int64_t workspace_bytes) {
+    const char* who = e.who;
+    const int64_t need = nm_optim_workspace_bytes(nchunk, nseg);
+    if (!e.itemised) NM_REQUIRE(theta && grad && slot0 && slot1 && workspace, "%s: null pointer", who);
+    NM_REQUIRE(kind >= e.kind_lo && kind <= e.kind_hi, "%s: kind %d (%s)", who, (int)kind, e.kinds);
+    if (!e.itemised) {
+        NM_REQUIRE(nchunk > 0 && nseg > 0 && workspace_bytes >= need, "%s: bad sizes", who);
+        return NM_OK;
+    }
+    NM_REQUIRE(theta && grad && workspace, "%s: null theta, grad or workspace", who);
+    NM_REQUIRE(has_tables(t), "%s: null table", who);
+    NM_REQUIRE(!opt_has0(kind) || slot0, "%s: kind %d needs slot0", who, (int)kind);
+    NM_REQUIRE(!opt_has1(kind) || slot1, "%s: kind %d needs slot1", who, (int)kind);
+    NM_REQUIRE(nchunk > 0 && nseg > 0 && nchunk <= 0x7fffffff, "%s: bad sizes nchunk %ld, nseg %ld", who, (long)nchunk,
+               (long)nseg);
+    if (workspace_bytes < need)
+        NM_FAIL(NM_ERR_WORKSPACE, "%s: workspace of %ld bytes, %ld needed", who, (long)workspace_bytes, (long)need);
+    return NM_OK;
+}
+
+// pass 3 behind all four entry points: the chunks [a, b) -- a range is the list-less case -- or the b of ``list``
+static int opt_update(const OptEntry& e, void* stream, int32_t kind, float* theta, const float* grad, float* slot0,
+                      float* slot1, OptChunks t, int64_t nchunk, int64_t nseg, float clip_norm, float p0, float p1,
+                      float p2, float p3, int64_t a, int64_t b, const int32_t* list, const int32_t* skip_word,
+                      void* workspace, int64_t workspace_bytes) {
+    int rc = opt_check(e, kind, theta, grad, slot0, slot1, t, nchunk, nseg, workspace, workspace_bytes);
+    if (rc != NM_OK) return rc;
+    unsigned grid;
+    rc = opt_select(e.who, e.by_list, a, b, list, nchunk, &grid);
+    if (rc != NM_OK || grid == 0) return rc;
+    // a slot the kind does not have never reaches its kernel; float4 rows only where every stream it touches allows
+    if (!opt_has0(kind)) slot0 = nullptr;
+    if (!opt_has1(kind)) slot1 = nullptr;
+    const int vec = nm_aligned16(theta) && nm_aligned16(grad) && nm_aligned16(slot0) && nm_aligned16(slot1);
+    static const decltype(&opt_update_kernel<OPT_ADAM>) kernels[] = {
+        opt_update_kernel<OPT_ADAM>,          opt_update_kernel<OPT_ADADELTA>,     opt_update_kernel<NM_OPTIM_SGD>,
+        opt_update_kernel<NM_OPTIM_MOMENTUM>, opt_update_kernel<NM_OPTIM_ADAGRAD>, opt_update_kernel<NM_OPTIM_RMSPROP>};
+    hipLaunchKernelGGL(kernels[kind], dim3(grid), dim3(256), 0, nm_stream(stream), t, theta, grad, slot0, slot1,
+                       reinterpret_cast<const float*>(workspace) + nchunk * 3, clip_norm, p0, p1, p2, p3, vec,
+                       e.by_list ? 0 : (int)a, skip_word, e.by_list ? list : nullptr);
+    NM_LAUNCH_CHECK(e.who);
+}
+
 // pass 3 over the chunks [chunk_begin, chunk_end): per-tensor clip + the optimizer's update.  kind 0: Adam
 // (p = lr_t, beta1, beta2, epsilon), kind 1: Adadelta (p = lr, rho, epsilon, -).  ``skip_word`` (may be null): a device
 // word that, when not zero, turns the launch into a no-op -- the session's error word (a GRU time loop gave up: the
@@ -233,23 +368,10 @@ extern "C" int nm_optim_apply(void* stream, int32_t kind, float* theta, const fl
                               int64_t nchunk, int64_t nseg, float clip_norm, float p0, float p1, float p2, float p3,
                               int64_t chunk_begin, int64_t chunk_end, const int32_t* skip_word, void* workspace,
                               int64_t workspace_bytes) {
-    NM_REQUIRE(theta && grad && slot0 && slot1 && workspace, "nm_optim_apply: null pointer");
-    NM_REQUIRE(kind == 0 || kind == 1, "nm_optim_apply: kind %d (0 Adam, 1 Adadelta)", (int)kind);
-    NM_REQUIRE(nchunk > 0 && nseg > 0 && workspace_bytes >= nm_optim_workspace_bytes(nchunk, nseg),
-               "nm_optim_apply: bad sizes");
-    NM_REQUIRE(chunk_begin >= 0 && chunk_begin <= chunk_end && chunk_end <= nchunk,
-               "nm_optim_apply: bad chunk range [%ld, %ld) of %ld", (long)chunk_begin, (long)chunk_end, (long)nchunk);
-    if (chunk_begin == chunk_end) return NM_OK;
-    OptChunks t = make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg);
-    const float* seg_norm2 = reinterpret_cast<const float*>(workspace) + nchunk * 3;
-    const unsigned grid = (unsigned)(chunk_end - chunk_begin);
-    if (kind == 0)
-        hipLaunchKernelGGL(opt_adam_kernel, dim3(grid), dim3(256), 0, nm_stream(stream), t, theta, grad, slot0, slot1,
-                           seg_norm2, clip_norm, p0, p1, p2, p3, (int)chunk_begin, skip_word, (const int*)nullptr);
-    else
-        hipLaunchKernelGGL(opt_adadelta_kernel, dim3(grid), dim3(256), 0, nm_stream(stream), t, theta, grad, slot0, slot1,
-                           seg_norm2, clip_norm, p0, p1, p2, (int)chunk_begin, skip_word, (const int*)nullptr);
-    NM_LAUNCH_CHECK("nm_optim_apply");
+    return opt_update(OPT_APPLY, stream, kind, theta, grad, slot0, slot1,
+                      make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg),
+                      nchunk, nseg, clip_norm, p0, p1, p2, p3, chunk_begin, chunk_end, nullptr, skip_word, workspace,
+                      workspace_bytes);
 }
 
 // ... over a list of chunks (see nm_optim_partials_list)
@@ -259,22 +381,35 @@ extern "C" int nm_optim_apply_list(void* stream, int32_t kind, float* theta, con
                                    int64_t nchunk, int64_t nseg, float clip_norm, float p0, float p1, float p2, float p3,
                                    const int32_t* chunk_list, int64_t count, const int32_t* skip_word, void* workspace,
                                    int64_t workspace_bytes) {
-    NM_REQUIRE(theta && grad && slot0 && slot1 && workspace, "nm_optim_apply_list: null pointer");
-    NM_REQUIRE(kind == 0 || kind == 1, "nm_optim_apply_list: kind %d (0 Adam, 1 Adadelta)", (int)kind);
-    NM_REQUIRE(nchunk > 0 && nseg > 0 && workspace_bytes >= nm_optim_workspace_bytes(nchunk, nseg),
-               "nm_optim_apply_list: bad sizes");
-    NM_REQUIRE(count >= 0 && count <= nchunk && (count == 0 || chunk_list), "nm_optim_apply_list: bad chunk list (%ld of %ld)",
-               (long)count, (long)nchunk);
-    if (count == 0) return NM_OK;
-    OptChunks t = make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg);
-    const float* seg_norm2 = reinterpret_cast<const float*>(workspace) + nchunk * 3;
-    if (kind == 0)
-        hipLaunchKernelGGL(opt_adam_kernel, dim3((unsigned)count), dim3(256), 0, nm_stream(stream), t, theta, grad, slot0,
-                           slot1, seg_norm2, clip_norm, p0, p1, p2, p3, 0, skip_word, chunk_list);
-    else
-        hipLaunchKernelGGL(opt_adadelta_kernel, dim3((unsigned)count), dim3(256), 0, nm_stream(stream), t, theta, grad, slot0,
-                           slot1, seg_norm2, clip_norm, p0, p1, p2, 0, skip_word, chunk_list);
-    NM_LAUNCH_CHECK("nm_optim_apply_list");
+    return opt_update(OPT_APPLY_LIST, stream, kind, theta, grad, slot0, slot1,
+                      make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg),
+                      nchunk, nseg, clip_norm, p0, p1, p2, p3, 0, count, chunk_list, skip_word, workspace,
+                      workspace_bytes);
+}
+
+// the same two for kinds 2..5 (nmhip_optim.h)
+extern "C" int nm_optim_update(void* stream, int32_t kind, float* theta, const float* grad, float* slot0, float* slot1,
+                               const int64_t* chunk_start, const int32_t* chunk_len, const int32_t* chunk_seg,
+                               const int32_t* seg_first, const int32_t* seg_count, const int32_t* seg_flags,
+                               int64_t nchunk, int64_t nseg, float clip_norm, float p0, float p1, float p2, float p3,
+                               int64_t chunk_begin, int64_t chunk_end, const int32_t* skip_word, void* workspace,
+                               int64_t workspace_bytes) {
+    return opt_update(OPT_UPDATE, stream, kind, theta, grad, slot0, slot1,
+                      make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg),
+                      nchunk, nseg, clip_norm, p0, p1, p2, p3, chunk_begin, chunk_end, nullptr, skip_word, workspace,
+                      workspace_bytes);
+}
+
+extern "C" int nm_optim_update_list(void* stream, int32_t kind, float* theta, const float* grad, float* slot0,
+                                    float* slot1, const int64_t* chunk_start, const int32_t* chunk_len,
+                                    const int32_t* chunk_seg, const int32_t* seg_first, const int32_t* seg_count,
+                                    const int32_t* seg_flags, int64_t nchunk, int64_t nseg, float clip_norm, float p0,
+                                    float p1, float p2, float p3, const int32_t* chunk_list, int64_t count,
+                                    const int32_t* skip_word, void* workspace, int64_t workspace_bytes) {
+    return opt_update(OPT_UPDATE_LIST, stream, kind, theta, grad, slot0, slot1,
+                      make_chunks(chunk_start, chunk_len, chunk_seg, seg_first, seg_count, seg_flags, nchunk, nseg),
+                      nchunk, nseg, clip_norm, p0, p1, p2, p3, 0, count, chunk_list, skip_word, workspace,
+                      workspace_bytes);
 }
 
 // x[0..n) = 0 when *word != 0 (the session's error word): a gradient that a given-up time loop left behind must not

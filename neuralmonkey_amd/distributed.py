@@ -589,9 +589,9 @@ class DataParallel:
         """Everything between the backward pass and the next forward pass: gradient exchange, regulariser terms and
         per-tensor norms, clip + update, and -- sharded -- the all-gather of the updated parameters.  ``tables``: the
         optimizer's chunk tables (ops.OptimizerTables built with ``optimizer_cuts``: ``partials`` / ``partial_vector`` /
-        ``segments`` / ``apply`` / ``chunk_range``); kind 0 Adam, 1 Adadelta, 2..5 the kinds of nmhip_optim.h (a slot such a kind lacks is
-        ``None``), ``params`` their four scalars; ``skip``:
-        the device word that voids the update (its maximum over ranks is taken here).  Returns the device [L1, L2]."""
+        ``segments`` / ``apply`` / ``chunk_range``); ``kind`` and ``params``: the optimizer's (optimizers.Optimizer.kind,
+        ``.params(step, applied)``; a slot the kind lacks is ``None``); ``skip``: the device word
+        that voids the update (its maximum over ranks is taken here).  Returns the device [L1, L2]."""
         grad = store.ensure_grad()
         self.all_reduce_gradients(store, error_word=skip)
         timed = self.timing and grad.is_cuda

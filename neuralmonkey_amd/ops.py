@@ -1455,47 +1455,31 @@ class OptimizerTables:
         return hit
 
     def apply(self, kind, theta, grad, slot0, slot1, clip_norm, params, skip=None, chunks=None, chunk_list=None):
-        """nm_optim_apply: kind 0 Adam (lr_t, beta1, beta2, epsilon), 1 Adadelta (lr, rho, epsilon, -); ``chunks``: a
-        (begin, end) range, ``chunk_list``: a device list of chunk indices (``chunk_list()``) in one launch.  Kinds 2..5
-        (optimizers.GradientDescentOptimizer.kind ...) are nm_optim_update's; a slot such a kind lacks is ``None``."""
-        lib = _lib.load()
-        p0, p1, p2, p3 = (float(x) for x in params)
-        if int(kind) >= 2:
-            c0, c1 = chunks if chunks is not None else (0, self.nchunk)
-            if chunk_list is not None:
-                name, select = "nm_optim_update_list", (chunk_list.data_ptr(), chunk_list.numel())
-            else:
-                name, select = "nm_optim_update", (int(c0), int(c1))
-            _lib.check(getattr(lib, name)(_stream(), int(kind), theta.data_ptr(), grad.data_ptr(), _p(slot0), _p(slot1),
-                                          *self._tabs(), float(clip_norm or 0.0), p0, p1, p2, p3, *select, _p(skip),
-                                          self.workspace.data_ptr(), self.workspace.numel() * 4), name)
-            return
+        """Pass 3, per-tensor clip + update of ``kind`` (optimizers.Optimizer.kind, with the four scalars of its
+        ``params``): nm_optim_apply for kinds 0 and 1, nm_optim_update for 2..5, whose missing slots are ``None``.
+        ``chunks``: a (begin, end) range (default: all), ``chunk_list``: a device list of chunk indices
+        (``chunk_list()``) in one launch."""
+        name = (("nm_optim_apply", "nm_optim_apply_list"),
+                ("nm_optim_update", "nm_optim_update_list"))[int(kind) >= 2][chunk_list is not None]
+        _lib.check(getattr(_lib.load(), name)(_stream(), int(kind), theta.data_ptr(), grad.data_ptr(), _p(slot0), _p(slot1),
+                                              *self._tabs(), float(clip_norm or 0.0), *(float(x) for x in params),
+                                              *self._select(chunks, chunk_list), _p(skip), self.workspace.data_ptr(),
+                                              self.workspace.numel() * 4), name)
+
+    def _select(self, chunks, chunk_list):
+        """The pair of arguments that names a launch's chunks: a device list and its length, or a range's two ends."""
         if chunk_list is not None:
-            _lib.check(lib.nm_optim_apply_list(_stream(), int(kind), theta.data_ptr(), grad.data_ptr(), slot0.data_ptr(),
-                                               slot1.data_ptr(), *self._tabs(), float(clip_norm or 0.0), p0, p1, p2, p3,
-                                               chunk_list.data_ptr(), chunk_list.numel(), _p(skip),
-                                               self.workspace.data_ptr(), self.workspace.numel() * 4),
-                       "nm_optim_apply_list")
-            return
+            return chunk_list.data_ptr(), chunk_list.numel()
         c0, c1 = chunks if chunks is not None else (0, self.nchunk)
-        _lib.check(lib.nm_optim_apply(_stream(), int(kind), theta.data_ptr(), grad.data_ptr(), slot0.data_ptr(),
-                                      slot1.data_ptr(), *self._tabs(), float(clip_norm or 0.0), p0, p1, p2, p3,
-                                      int(c0), int(c1), _p(skip), self.workspace.data_ptr(),
-                                      self.workspace.numel() * 4), "nm_optim_apply")
+        return int(c0), int(c1)
 
     def partials(self, theta, grad, l1_weight, l2_weight, chunks, chunk_list=None):
         """Pass 1 over the chunks [begin, end) -- or over a device list of chunks: regulariser terms into ``grad``,
         partial sums into the workspace."""
-        lib = _lib.load()
-        if chunk_list is not None:
-            _lib.check(lib.nm_optim_partials_list(_stream(), theta.data_ptr(), grad.data_ptr(), *self._tabs(),
-                                                  float(l1_weight), float(l2_weight), chunk_list.data_ptr(),
-                                                  chunk_list.numel(), self.workspace.data_ptr(),
-                                                  self.workspace.numel() * 4), "nm_optim_partials_list")
-            return
-        _lib.check(lib.nm_optim_partials(_stream(), theta.data_ptr(), grad.data_ptr(), *self._tabs(),
-                                         float(l1_weight), float(l2_weight), int(chunks[0]), int(chunks[1]),
-                                         self.workspace.data_ptr(), self.workspace.numel() * 4), "nm_optim_partials")
+        name = ("nm_optim_partials", "nm_optim_partials_list")[chunk_list is not None]
+        _lib.check(getattr(_lib.load(), name)(_stream(), theta.data_ptr(), grad.data_ptr(), *self._tabs(),
+                                              float(l1_weight), float(l2_weight), *self._select(chunks, chunk_list),
+                                              self.workspace.data_ptr(), self.workspace.numel() * 4), name)
 
     def partial_vector(self):
         """The 3 floats per chunk that ``partials`` writes (a view of the workspace)."""

@@ -1,9 +1,11 @@
 """Optimizer descriptions (stand-ins for the tf.train.* objects INI files name).
 
-The update itself is a fused clip + update HIP kernel over the flat parameter buffer
-(csrc/nm_optim.hip: Adam, Adadelta; csrc/nm_optim_family.hip: GradientDescent, Momentum,
-Adagrad, RMSProp); these classes only carry hyper-parameters and the names of the slot
-variables -- none, one or two -- a TensorFlow checkpoint holds per variable (``slot_suffixes``)."""
+The update itself is one fused clip + update HIP kernel over the flat parameter buffer
+(csrc/nm_optim.hip, one instantiation per ``kind``); these classes only carry what the trainer
+reads: ``kind`` (0..5), ``params(step, applied)`` -- the four scalars of the update --
+``slot_initial`` and the names of the slot variables -- none, one or two -- a TensorFlow
+checkpoint holds per variable (``slot_suffixes``, ``<var>/<name>`` and ``<var>/<name>_1`` as
+TensorFlow's slot creator makes them)."""
 import math
 from typing import Callable, Union
 
@@ -11,12 +13,23 @@ from .checking import check_argument_types
 
 
 class Optimizer:
+    kind = -1
     slot_suffixes = ("/Adam", "/Adam_1")
     slot_initial = (0.0, 0.0)          # the value each slot starts at
+
+    def learning_rate(self, step: int) -> float:
+        """Learning rate of update number ``step`` (1-based).  A schedule is evaluated at the
+        global step before the update, as the TF graph does (functions.py)."""
+        return float(self._lr(step - 1)) if callable(self._lr) else float(self._lr)
+
+    def params(self, step: int, applied: int = None):
+        """(p0, p1, p2, p3) of update number ``step``; ``applied``: see ``AdamOptimizer.lr_t``."""
+        raise NotImplementedError
 
 
 class AdamOptimizer(Optimizer):
     """tf.train.AdamOptimizer: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; theta -= lr_t*m/(sqrt(v)+eps)."""
+    kind = 0
 
     def __init__(self, learning_rate: Union[float, Callable[[int], float]] = 0.001, beta1: float = 0.9,
                  beta2: float = 0.999, epsilon: float = 1e-8, use_locking: bool = False,
@@ -24,17 +37,15 @@ class AdamOptimizer(Optimizer):
         self._lr = learning_rate
         self.beta1, self.beta2, self.epsilon = beta1, beta2, epsilon
 
-    def learning_rate(self, step: int) -> float:
-        """Learning rate of update number ``step`` (1-based).  A schedule is evaluated at the
-        global step before the update, as the TF graph does (functions.py)."""
-        return float(self._lr(step - 1)) if callable(self._lr) else float(self._lr)
-
     def lr_t(self, step: int, applied: int = None) -> float:
         """``step`` counts from 1 (the value of global_step after this update) and drives the learning
         rate schedule; ``applied`` is the number of updates this optimizer has applied including this
         one (TF keeps beta1_power / beta2_power per optimizer) -- equal to ``step`` with one trainer."""
         t = step if applied is None else applied
         return self.learning_rate(step) * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
+
+    def params(self, step: int, applied: int = None):
+        return (self.lr_t(step, applied), self.beta1, self.beta2, self.epsilon)
 
 
 class LazyAdamOptimizer(AdamOptimizer):
@@ -48,6 +59,7 @@ class AdadeltaOptimizer(Optimizer):
     accum = rho*accum + (1-rho)*g^2;  update = sqrt(accum_update + eps) * rsqrt(accum + eps) * g;
     var -= lr*update;  accum_update = rho*accum_update + (1-rho)*update^2.  The slots are created under the
     optimizer's ``name``: ``<var>/<name>`` (accum) and ``<var>/<name>_1`` (accum_update)."""
+    kind = 1
 
     def __init__(self, learning_rate: Union[float, Callable[[int], float]] = 0.001, rho: float = 0.95,
                  epsilon: float = 1e-8, use_locking: bool = False, name: str = "Adadelta") -> None:
@@ -55,26 +67,15 @@ class AdadeltaOptimizer(Optimizer):
         self.rho, self.epsilon = rho, epsilon
         self.slot_suffixes = ("/" + name, "/" + name + "_1")
 
-    def learning_rate(self, step: int) -> float:
-        """As ``AdamOptimizer.learning_rate``: a schedule is evaluated at the global step before the update."""
-        return float(self._lr(step - 1)) if callable(self._lr) else float(self._lr)
+    def params(self, step: int, applied: int = None):
+        return (self.learning_rate(step), self.rho, self.epsilon, 0.0)
 
 
 class _FamilyOptimizer(Optimizer):
-    """What the trainer reads from the optimizers whose update is nm_optim_update (include/nmhip_optim.h):
-    ``kind`` (2..5), ``slot_suffixes`` (0, 1 or 2 names, ``<var>/<name>`` and ``<var>/<name>_1`` as TensorFlow's slot
-    creator makes them), ``slot_initial`` (the value each slot starts at) and ``params(step)``, the four scalars of
-    the update.  None of them keeps beta powers in a checkpoint."""
-    kind = -1
+    """The optimizers of kinds 2..5 (include/nmhip_optim.h): no slot unless the class names one, and no beta powers
+    in a checkpoint, so ``params`` ignores ``applied``."""
     slot_suffixes = ()
     slot_initial = ()
-
-    def learning_rate(self, step: int) -> float:
-        """As ``AdamOptimizer.learning_rate``: a schedule is evaluated at the global step before the update."""
-        return float(self._lr(step - 1)) if callable(self._lr) else float(self._lr)
-
-    def params(self, step: int):
-        raise NotImplementedError
 
 
 class GradientDescentOptimizer(_FamilyOptimizer):
@@ -86,7 +87,7 @@ class GradientDescentOptimizer(_FamilyOptimizer):
         check_argument_types()
         self._lr = learning_rate
 
-    def params(self, step: int):
+    def params(self, step: int, applied: int = None):
         return (self.learning_rate(step), 0.0, 0.0, 0.0)
 
 
@@ -103,7 +104,7 @@ class MomentumOptimizer(_FamilyOptimizer):
         self.slot_suffixes = ("/" + name,)
         self.slot_initial = (0.0,)
 
-    def params(self, step: int):
+    def params(self, step: int, applied: int = None):
         return (self.learning_rate(step), self.momentum, 1.0 if self.use_nesterov else 0.0, 0.0)
 
 
@@ -122,7 +123,7 @@ class AdagradOptimizer(_FamilyOptimizer):
         self.slot_suffixes = ("/" + name,)
         self.slot_initial = (self.initial_accumulator_value,)
 
-    def params(self, step: int):
+    def params(self, step: int, applied: int = None):
         return (self.learning_rate(step), 0.0, 0.0, 0.0)
 
 
@@ -142,5 +143,5 @@ class RMSPropOptimizer(_FamilyOptimizer):
         self.slot_suffixes = ("/" + name, "/" + name + "_1")
         self.slot_initial = (1.0, 0.0)
 
-    def params(self, step: int):
+    def params(self, step: int, applied: int = None):
         return (self.learning_rate(step), self.decay, self.momentum, self.epsilon)

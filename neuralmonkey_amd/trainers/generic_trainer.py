@@ -224,9 +224,9 @@ class GenericTrainer(GraphExecutor, Feedable):
         sess.join_side()
 
     def _apply_gradients(self, ctx) -> int:
-        """[gradient exchange] -> L1/L2 terms -> per-tensor clip_by_norm -> Adam / Adadelta -> [parameter all-gather]
-        -> global_step += 1.  With data parallelism the exchange and the update are distributed.DataParallel's
-        (replicated, or sharded over the ranks' slices of the flat buffers)."""
+        """[gradient exchange] -> L1/L2 terms -> per-tensor clip_by_norm -> the optimizer's update -> [parameter
+        all-gather] -> global_step += 1.  With data parallelism the exchange and the update are
+        distributed.DataParallel's (replicated, or sharded over the ranks' slices of the flat buffers)."""
         from .. import distributed as dist
         sess, store = ctx.session, ctx.store
         grad = store.ensure_grad()
@@ -235,13 +235,7 @@ class GenericTrainer(GraphExecutor, Feedable):
         state = self._adam_state(sess, store)
         sess.global_step += 1
         state["applied"] += 1
-        opt = self.optimizer
-        if isinstance(opt, AdadeltaOptimizer):
-            kind, params = 1, (opt.learning_rate(sess.global_step), opt.rho, opt.epsilon, 0.0)
-        elif not isinstance(opt, AdamOptimizer):         # GradientDescent, Momentum, Adagrad, RMSProp describe themselves
-            kind, params = opt.kind, opt.params(sess.global_step)
-        else:
-            kind, params = 0, (opt.lr_t(sess.global_step, state["applied"]), opt.beta1, opt.beta2, opt.epsilon)
+        kind, params = self.optimizer.kind, self.optimizer.params(sess.global_step, state["applied"])
         # the update is a no-op on the device while the session's error word is set (a time loop of this step gave up:
         # the gradient is garbage, Session.recover_training runs the step again)
         skip = sess.error_word() if sess.device.type == "cuda" else None

@@ -1,5 +1,5 @@
 """The clip + update kernels of GradientDescent, Momentum (plain and Nesterov), Adagrad and RMSProp
-(include/nmhip_optim.h, csrc/nm_optim_family.hip): called directly over the flat buffers of
+(include/nmhip_optim.h, kinds 2..5 of csrc/nm_optim.hip's update kernel): called directly over the flat buffers of
 tests/test_pointwise_kernels_gpu.py against the float64 restatement (tests/optim_ref.py), and behind the trainer against
 the oracle's gradients plus the restatement, with a checkpoint round trip.  tests/test_optim_family_host.py shows on the
 CPU that a float32 evaluation of the restatement meets the direct test's bound on the same inputs."""
@@ -20,7 +20,7 @@ def _passes(tables, d, kind, params, path, skip=None):
     from .test_pointwise_kernels_gpu import i32
     s0 = d["s0"] if R.SLOTS[kind] >= 1 else None
     s1 = d["s1"] if R.SLOTS[kind] == 2 else None
-    if path == "whole":
+    if path.startswith("whole"):
         tables.regularize_and_norms(d["theta"], d["grad"], OC.L1W, OC.L2W)
         tables.apply(kind, d["theta"], d["grad"], s0, s1, OC.CLIP, params, skip=skip)
     elif path == "ranges":
@@ -53,18 +53,19 @@ def cases():
     return get
 
 
-@pytest.mark.parametrize("path", OC.PATHS)
+@pytest.mark.parametrize("path", OC.PATHS + ("whole-cut",))
 @pytest.mark.parametrize("variant", sorted(OC.VARIANTS))
 def test_family_kernels_direct(dev, cases, variant, path):
-    """nm_optim_update / nm_optim_update_list behind nm_optim.hip's passes 1 and 2, two consecutive updates (the second
-    reads the accumulators the first wrote): regularised gradient, parameters and every slot the kind has against
-    float64 within 2e-5 x the tensor's largest entry; the frozen variable, the padding and the slots the kind lacks
-    (passed as NULL) bit-unchanged."""
-    from .test_pointwise_kernels_gpu import _optimizer_setup
+    """nm_optim_update / nm_optim_update_list behind passes 1 and 2, two consecutive updates (the second reads the
+    accumulators the first wrote): regularised gradient, parameters and every slot the kind has against float64 within
+    2e-5 x the tensor's largest entry; the frozen variable, the padding and the slots the kind lacks (passed as NULL)
+    bit-unchanged.  ``whole-cut``: the whole table once more, cut inside w_a (``W_A_CUT``) so that two of its chunks
+    start at odd element offsets and run the scalar loops from end to end."""
+    from .test_pointwise_kernels_gpu import W_A_CUT, _optimizer_setup
     kind, params = OC.VARIANTS[variant]
     specs, host, want = cases(variant)
-    _, tables, again = _optimizer_setup(dev, OC.seed_of(variant))
-    assert tables.nchunk >= 5 and np.array_equal(again["theta"], host["theta"])
+    _, tables, again = _optimizer_setup(dev, OC.seed_of(variant), cuts=W_A_CUT if path == "whole-cut" else ())
+    assert tables.nchunk == (6 if path == "whole-cut" else 5) and np.array_equal(again["theta"], host["theta"])
     d = {k: torch.tensor(host[k], device=dev) for k in ("theta", "grad", "s0", "s1")}
     for step, key in enumerate(("grad", "grad2")):
         d["grad"].copy_(torch.tensor(host[key], device=dev))

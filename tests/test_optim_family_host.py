@@ -1,5 +1,5 @@
 """GradientDescent, Momentum, Adagrad and RMSProp without a GPU: the tf.train.* names through the config loader,
-constructor signatures and refusals, the NumPy restatement (tests/optim_ref.py) against the formulas written out and
+constructor signatures and refusals, ``kind`` / ``params`` of Adam and Adadelta beside them, the NumPy restatement (tests/optim_ref.py) against the formulas written out and
 against torch.optim, the float32 headroom of the direct GPU test's bound on its exact inputs, the binding table of
 include/nmhip_optim.h with its refusals, and checkpoints with none, one or two slot variables per variable."""
 import ctypes
@@ -97,6 +97,29 @@ def test_constructors_defaults_and_refusals():
         RMSPropOptimizer(0.1, decay=None)
     with pytest.raises(TypeError):
         MomentumOptimizer(0.1)                                   # momentum has no default, as in TensorFlow
+
+
+def test_adam_and_adadelta_describe_themselves_as_the_family_does():
+    """``kind`` and ``params(step, applied)`` of the two optimizers of nm_optim_apply against their formulas written
+    out, for a constant and a callable learning rate: Adam's bias correction counts the updates THIS optimizer applied,
+    its schedule (evaluated at the global step before the update) follows ``step``."""
+    import math
+    from neuralmonkey_amd.optimizers import AdadeltaOptimizer, AdamOptimizer, LazyAdamOptimizer
+    b1, b2, eps = 0.8, 0.99, 1e-7
+    for lr, at in ((0.25, lambda step: 0.25), (lambda s: 1.0 / (s + 1), lambda step: 1.0 / step)):
+        adam = AdamOptimizer(lr, beta1=b1, beta2=b2, epsilon=eps)
+        assert adam.kind == 0 and LazyAdamOptimizer(lr).kind == 0
+        for step, applied, t in ((1, None, 1), (6, None, 6), (6, 6, 6), (6, 3, 3)):
+            want = (at(step) * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t), b1, b2, eps)
+            assert adam.params(step, applied) == want, (step, applied)
+        assert adam.params(6, 3) != adam.params(6) and adam.params(6, 3)[0] == adam.lr_t(6, 3)
+        delta = AdadeltaOptimizer(lr, rho=0.9, epsilon=1e-6, name="delta")
+        assert delta.kind == 1 and delta.slot_suffixes == ("/delta", "/delta_1")
+        for step in (1, 6):
+            assert delta.params(step) == delta.params(step, 2) == (at(step), 0.9, 1e-6, 0.0)
+    # the family takes the same call and ignores the count
+    from neuralmonkey_amd.optimizers import MomentumOptimizer
+    assert MomentumOptimizer(0.1, 0.8).params(4, 2) == MomentumOptimizer(0.1, 0.8).params(4) == (0.1, 0.8, 0.0, 0.0)
 
 
 def test_centered_rmsprop_constructs_and_is_refused_by_the_trainer(tmp_path):

@@ -727,18 +727,23 @@ class _Spec:
         self.size, self.offset = size, offset
 
 
-def _optimizer_setup(dev, seed):
-    """A flat parameter buffer of four variables (one longer than a chunk, padded offsets) and its tables."""
+W_A_CUT = (1001,)     # a shard's cut inside w_a: chunks of 1001 (a 1-element tail), 65536 and 3464, the last two at odd offsets
+
+
+def _optimizer_setup(dev, seed, cuts=(), small=False):
+    """A flat parameter buffer of four variables (one longer than a chunk, padded offsets) and its tables, cut at the
+    flat offsets ``cuts`` as well; ``small``: without the long variable."""
     from collections import OrderedDict
     from types import SimpleNamespace
     from neuralmonkey_amd import ops
-    sizes = OrderedDict([("w_a", 70001), ("bias_b", 37), ("frozen", 500), ("w_c", 1031)])
+    sizes = OrderedDict([("w_a", 70001), ("bias_b", 37), ("frozen", 500), ("w_c", 1031)][1 if small else 0:])
     specs, off = OrderedDict(), 0
     for name, size in sizes.items():
         specs[name] = _Spec(size, off)
         off += (size + 3) // 4 * 4
     store = SimpleNamespace(specs=specs, device=dev)
-    tables = ops.OptimizerTables(store, regularizable={"w_a", "frozen", "w_c"}, trainable={"w_a", "bias_b", "w_c"})
+    tables = ops.OptimizerTables(store, regularizable={"w_a", "frozen", "w_c"}, trainable={"w_a", "bias_b", "w_c"},
+                                 cuts=cuts)
     rng = np.random.default_rng(seed)
     flat = lambda scale, positive=False: (np.abs(rng.standard_normal(off)) if positive else rng.standard_normal(off)) \
         .astype(np.float32) * np.float32(scale)
@@ -751,11 +756,12 @@ def _optimizer_reference(specs, host, kind, l1w, l2w, clip, params):
     from oracle import torch_ref as TR
     view = lambda buf, sp: torch.tensor(buf[sp.offset:sp.offset + sp.size], dtype=torch.float64)
     p, g, s0, s1 = ({n: view(host[k], sp) for n, sp in specs.items()} for k in ("theta", "grad", "s0", "s1"))
-    for n in ("w_a", "frozen", "w_c"):
+    reg = [n for n in ("w_a", "frozen", "w_c") if n in specs]
+    for n in reg:
         g[n] = g[n] + l1w * torch.sign(p[n]) + 2.0 * l2w * p[n]
-    l1 = sum(float(p[n].abs().sum()) for n in ("w_a", "frozen", "w_c"))
-    l2 = sum(float((p[n] ** 2).sum()) for n in ("w_a", "frozen", "w_c"))
-    train = ("w_a", "bias_b", "w_c")
+    l1 = sum(float(p[n].abs().sum()) for n in reg)
+    l2 = sum(float((p[n] ** 2).sum()) for n in reg)
+    train = [n for n in ("w_a", "bias_b", "w_c") if n in specs]
     sub = lambda d: {n: d[n] for n in train}
     pt, s0t, s1t = sub(p), sub(s0), sub(s1)
     if kind == 0:
@@ -773,21 +779,23 @@ def _optimizer_reference(specs, host, kind, l1w, l2w, clip, params):
 
 
 @pytest.mark.parametrize("kind", [0, 1])
-@pytest.mark.parametrize("path", ["whole", "ranges", "lists"])
+@pytest.mark.parametrize("path", ["whole", "ranges", "lists", "whole-cut"])
 def test_optimizer_kernels_direct(dev, kind, path):
     """The flat optimizer kernels called directly: nm_optim_regularize_norms + nm_optim_clip_adam / _clip_adadelta
     (one call each), nm_optim_partials + _segments + _apply over two chunk ranges, and the _list forms over a shuffled
     chunk list -- regularised gradient, L1 / L2, both slots and the parameters against float64; frozen and padding
-    elements untouched."""
+    elements untouched.  ``whole-cut``: the first once more over a table cut inside w_a (``W_A_CUT``), whose chunks at
+    odd element offsets run the kernels' scalar loops from end to end."""
     from neuralmonkey_amd import _lib, ops
     lib = _lib.load()
-    specs, tables, host = _optimizer_setup(dev, 11 + kind)
+    specs, tables, host = _optimizer_setup(dev, 11 + kind, cuts=W_A_CUT if path == "whole-cut" else ())
+    assert tables.nchunk == (6 if path == "whole-cut" else 5)
     if kind == 1:
         host["s0"] = np.abs(host["s0"])             # Adadelta's accumulators are sums of squares
     l1w, l2w, clip = 1e-3, 1e-2, 1.0
     params = (1e-3, 0.9, 0.999, 1e-8) if kind == 0 else (0.5, 0.95, 1e-6, 0.0)
     d = {k: torch.tensor(v, device=dev) for k, v in host.items()}
-    if path == "whole":
+    if path.startswith("whole"):
         l1l2 = tables.regularize_and_norms(d["theta"], d["grad"], l1w, l2w)
         fn = lib.nm_optim_clip_adam if kind == 0 else lib.nm_optim_clip_adadelta
         args = params if kind == 0 else params[:3]
@@ -823,6 +831,54 @@ def test_optimizer_kernels_direct(dev, kind, path):
         if n == "frozen":
             assert all(np.array_equal(got[key][sl], host[key][sl]) for key in ("theta", "s0", "s1"))
     assert all(np.array_equal(got[key][~covered], host[key][~covered]) for key in got)
+
+
+@pytest.mark.parametrize("variant", ["sgd", "momentum", "adam"])
+def test_optimizer_kernels_on_buffers_off_16_bytes(dev, variant):
+    """One kind per slot count (none, one, two) over buffers that are 4-byte but not 16-byte aligned: every device buffer
+    is the [1:] view of one an element longer.  The variables are the small ones, whose chunks all start on a multiple
+    of four elements, so it is the buffers' addresses alone that must keep passes 1 and 3 off their float4 rows.  One
+    update against float64 within 2e-5 x the tensor's largest entry; the frozen variable, the padding, the slots the
+    kind lacks and the element in front of every buffer bit-unchanged."""
+    from tests import optim_family_cases as OC
+    keys = ("theta", "grad", "s0", "s1")
+    specs, tables, host = _optimizer_setup(dev, 41, small=True)
+    assert "w_a" not in specs and tables.nchunk == 3
+    if variant == "adam":
+        kind, slots, params = 0, 2, (1e-3, 0.9, 0.999, 1e-8)
+        refs = _optimizer_reference(specs, host, kind, OC.L1W, OC.L2W, OC.CLIP, params)[:4]
+        want = {key: {n: C.np64(ref[n]) for n in specs} for key, ref in zip(keys, refs)}
+    else:
+        from tests import optim_ref as R
+        kind, params = OC.VARIANTS[variant]
+        slots = R.SLOTS[kind]
+        flat = OC.expected(specs, OC.prepare(host, variant), variant)[0]
+        want = {key: {n: flat[key][sp.offset:sp.offset + sp.size] for n, sp in specs.items()} for key in keys}
+    full = {k: torch.full((host[k].size + 1,), NAN, device=dev) for k in keys}
+    d = {k: v[1:] for k, v in full.items()}
+    for k in keys:
+        d[k].copy_(torch.tensor(host[k]))
+    assert all(v.data_ptr() % 16 == 4 for v in d.values())
+    tables.regularize_and_norms(d["theta"], d["grad"], OC.L1W, OC.L2W)
+    tables.apply(kind, d["theta"], d["grad"], d["s0"] if slots >= 1 else None, d["s1"] if slots == 2 else None, OC.CLIP,
+                 params)
+    assert all(bool(torch.isnan(v[0])) for v in full.values())
+    got = {k: v.cpu().numpy() for k, v in d.items()}
+    covered = np.zeros(got["theta"].size, dtype=bool)
+    for n, sp in specs.items():
+        sl = slice(sp.offset, sp.offset + sp.size)
+        covered[sl] = True
+        for key in keys:
+            err, bound = np.abs(got[key][sl] - want[key][n]).max(), 2e-5 * np.abs(want[key][n]).max()
+            print("{} {} {}: err {:.3g} bound {:.3g}".format(variant, n, key, err, bound))
+            assert err <= bound, (variant, n, key, err, bound)
+        if n == "frozen":
+            assert all(np.array_equal(got[key][sl], host[key][sl]) for key in ("theta", "s0", "s1"))
+        else:
+            assert not np.array_equal(got["theta"][sl], host["theta"][sl])
+    assert not covered.all() and all(np.array_equal(got[key][~covered], host[key][~covered]) for key in keys)
+    for key, has in (("s0", slots >= 1), ("s1", slots == 2)):
+        assert has or np.array_equal(got[key], host[key])
 
 
 

@@ -1,7 +1,7 @@
 """HIP-event timings of the optimizers' clip + update launch (pass 3 of the flat optimizer) on the flat buffers of the
 headline model -- bench.py's training configuration: vocabulary 32000, hidden 512; the element count is read from the
-store -- for Adam (kind 0, csrc/nm_optim.hip) and GradientDescent, Momentum, Adagrad, RMSProp (kinds 2..5,
-csrc/nm_optim_family.hip).
+store -- for Adam (kind 0) and GradientDescent, Momentum, Adagrad, RMSProp (kinds 2..5), all instantiations of
+csrc/nm_optim.hip's update kernel.
 
 Per element an update moves 4-byte streams: Adam and RMSProp 7 (theta, both slots read and written; the gradient
 read), Momentum and Adagrad 5, GradientDescent 3.  The table gives, per kind, the median microseconds per update, the
