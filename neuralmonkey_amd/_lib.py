@@ -268,6 +268,12 @@ IMGREAD_SIGNATURES = {
     "nm_imgread_check": (I, [P, P, L, I, L, L]),
 }
 
+# ... and every symbol include/nmhip_vgg.h declares (the frozen ImageNet networks' convolution + bias + ReLU,
+# csrc/nm_vgg.hip)
+VGG_SIGNATURES = {
+    "nm_conv2d_act_fwd": (I, [P, P, L, L, L, L, L, P, L, L, I, P, I, P, L, I]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -341,7 +347,7 @@ def load():
                               + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
                               + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
                               + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
-                              + list(IMGREAD_SIGNATURES.items())):
+                              + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -2249,6 +2249,27 @@ def map_columns(src, dst, inverse=False):
     return dst
 
 
+# ---- the frozen ImageNet networks (include/nmhip_vgg.h, csrc/nm_vgg.hip) ----------------------------------------------------
+CONV_ACT_TILES = {None: 0, "auto": 0, "128x64": 1, "64x64": 2}
+
+
+def conv2d_act_fwd(x, filt, bias, y, padding, relu=True, tile=None):
+    """y [B, OH, OW, Cout] = act(conv2d(x [B, H, W, Cin], filt [k, k, Cin, Cout]) + bias) at stride 1, forward only
+    (nm_conv2d_act_fwd): act is the ReLU or, with ``relu=False``, nothing; ``bias`` may be None."""
+    bsz, h, w, cin, ldx = _nhwc(x, "conv2d_act_fwd x")
+    _f32(filt)
+    assert filt.dim() == 4 and filt.is_contiguous() and filt.shape[0] == filt.shape[1] and filt.shape[2] == cin, "filter"
+    k, cout = int(filt.shape[0]), int(filt.shape[3])
+    assert bias is None or (_f32(bias).is_contiguous() and bias.numel() == cout)
+    oh, ow = conv2d_out_hw(h, w, k, padding)
+    assert tuple(y.shape) == (bsz, oh, ow, cout), (tuple(y.shape), (bsz, oh, ow, cout))
+    ldy = _nhwc(y, "conv2d_act_fwd y")[4]
+    _lib.check(_lib.load().nm_conv2d_act_fwd(_stream(), x.data_ptr(), ldx, bsz, h, w, cin, filt.data_ptr(), k, cout,
+                                             PADDINGS[padding], _p(bias), int(bool(relu)), y.data_ptr(), ldy,
+                                             CONV_ACT_TILES[tile]), "nm_conv2d_act_fwd")
+    return y
+
+
 # ---- rewards of self-critical training (include/nmhip_reward.h, csrc/nm_reward.hip) ----------------------------------------
 REWARD_KINDS = {"bleu": 0, "gleu": 1}
 
