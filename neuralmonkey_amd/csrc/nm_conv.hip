@@ -21,7 +21,8 @@
 //   conv_wgrad_mfma   weight gradient per (width, tap, 64 channels, 64 filters) tile, positions split over
 //                     workgroups into fixed slabs that conv_wgrad_reduce sums in a fixed order: no float atomics,
 //                     repeated runs are bit-identical.
-//   *_generic         scalar kernels for shapes the MFMA path does not take (w > 8, s > 128, > 16 widths).
+//   *_generic         scalar kernels for shapes the MFMA path does not take (w > 8, s > 128).  No kernel takes more
+//                     than 16 filter widths (CONV_MAX_WIDTHS, the table in ConvArgs): conv_setup refuses them.
 //   convs2s_*         the residual layer of the convolutional sequence-to-sequence encoder (facebook_conv.py): the same
 //                     implicit GEMM with a GLU + residual epilogue in registers; its gradients reuse conv_mfma<true>
 //                     and the weight-gradient kernels through conv_grads_launch (further down).

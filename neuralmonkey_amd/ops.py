@@ -1571,6 +1571,8 @@ def highway_fwd(zt, zh, x, bt, bh, y, tsave, hsave):
     """y = relu(zh + bh) T + x (1 - T), T = sigmoid(zt + bt) (nm_highway_fwd); T, H kept for the backward pass."""
     rows, cols, ldx = _rc(x)
     assert _rc(y)[2] == ldx and _rc(zh)[2] == _rc(zt)[2] and tsave.is_contiguous() and hsave.is_contiguous()
+    if rows == 0:                     # (an empty tensor has a null data pointer, which the entry point refuses)
+        return y
     _lib.check(_lib.load().nm_highway_fwd(_stream(), zt.data_ptr(), zh.data_ptr(), _rc(zt)[2], x.data_ptr(), ldx,
                                           bt.data_ptr(), bh.data_ptr(), y.data_ptr(), tsave.data_ptr(),
                                           hsave.data_ptr(), rows, cols), "nm_highway_fwd")
@@ -1581,6 +1583,8 @@ def highway_bwd(dy, x, tsave, hsave, dzt, dzh, dx, accumulate_dx=False):
     """dzt, dzh (the gradients of the two products' outputs) and the carry term of dx (nm_highway_bwd)."""
     rows, cols, ldx = _rc(x)
     assert _rc(dy)[2] == ldx and _rc(dx)[2] == ldx and _rc(dzh)[2] == _rc(dzt)[2]
+    if rows == 0:
+        return
     _lib.check(_lib.load().nm_highway_bwd(_stream(), dy.data_ptr(), x.data_ptr(), ldx, tsave.data_ptr(),
                                           hsave.data_ptr(), dzt.data_ptr(), dzh.data_ptr(), _rc(dzt)[2], dx.data_ptr(),
                                           rows, cols, int(accumulate_dx)), "nm_highway_bwd")

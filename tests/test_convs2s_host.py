@@ -317,6 +317,16 @@ def test_convs2s_entry_points_refuse_before_any_launch(lib):
     assert lib.nm_conv1d_glu_workspace_bytes(16, 256, 512, 5) > 5 * 512 * 1024 * 4    # several position slices
     for bad in ((0, 3, 8, 5), (2, 0, 8, 5), (2, 3, 0, 5), (2, 3, 8, 0), (1 << 31, 3, 8, 5)):
         assert lib.nm_conv1d_glu_workspace_bytes(*bad) == 0
+    # the slab plan of the shared weight gradient (tests/conv1d_ref.py): the GPU cases G1-G3 take two to four slabs, the
+    # largest of the older cases (2 x 131, C 200, w 5) one
+    from .conv1d_ref import GLU_SLAB_CASES, glu_filters, slab_plan
+    for name, ((bsz, steps, c, width), tiles, slices, per, last) in GLU_SLAB_CASES.items():
+        plan = slab_plan(bsz, steps, c, glu_filters(c, width))
+        assert (plan["tiles"], plan["slices"], plan["per"], plan["last"]) == (tiles, slices, per, last), (name, plan)
+        assert lib.nm_conv1d_glu_workspace_bytes(bsz, steps, c, width) == slices * width * c * 2 * c * 4, name
+    assert all(GLU_SLAB_CASES[name][3] == GLU_SLAB_CASES[name][0][1] for name in ("G2", "G3"))    # seams on sentence seams
+    assert slab_plan(2, 131, 200, glu_filters(200, 5))["slices"] == 1
+    assert lib.nm_conv1d_glu_workspace_bytes(2, 131, 200, 5) == 5 * 200 * 400 * 4
 
     def bwd(x=buf, ldx=8, b=2, t=3, c=8, w=5, filt=third, lin=save, sig=save, dy=other, lddy=8, dz=third, dx=None,
             lddx=8, acc=0, dw=None, db=None, accp=0, ws=None, ws_bytes=0, algo=0):

@@ -3,24 +3,17 @@ fused conv1d + GLU + residual kernels (MFMA and scalar) and their gradients agai
 taped functions built on them (autodiff.conv1d_glu, add_position_param, time_max) against float64 autograd.
 
 Tolerances are built the way tests/test_sentence_cnn_gpu.py builds them: 1e-6 times the same expression evaluated on
-the absolute values of the operands (sigmoid bounded by 1, sigmoid' by 1/4) plus 1e-7, times 10."""
+the absolute values of the operands (sigmoid bounded by 1, sigmoid' by 1/4) plus 1e-7, times 10.  The test of the
+weight gradient's slab path uses the derived summation bound of tests/conv1d_ref.py instead."""
 import math
 
 import pytest
 import torch
-import torch.nn.functional as TF
 
-from .test_sentence_cnn_gpu import _ref_conv_t, _ref_wgrad
+from . import conv1d_ref as R
+from .conv1d_ref import _pre, _ref_conv_t, _ref_wgrad
 
 pytestmark = pytest.mark.gpu
-
-
-def _pre(x, w, b):
-    """tf.nn.conv1d(x, w, 1, "SAME") + b in float64: x [B, T, C], w [width, C, 2C] -> [B, T, 2C]."""
-    width = w.shape[0]
-    pad = (width - 1) // 2
-    xp = TF.pad(x.transpose(1, 2), (pad, width - 1 - pad))
-    return TF.conv1d(xp, w.permute(2, 1, 0)).transpose(1, 2) + b
 
 
 def _tol(scale):
@@ -136,6 +129,91 @@ def test_glu_layer_forward_and_gradients_match_float64(dev, case):
     assert torch.equal(dx4, dx3)
 
 
+SLAB_RUNS = [("G1", (0, 0, 0, 0)), ("G1", (3, 5, 2, 7)), ("G2", (0, 0, 0, 0)), ("G3", (0, 0, 0, 0))]
+
+
+@pytest.mark.parametrize("name,pads", SLAB_RUNS, ids=lambda v: v if isinstance(v, str) else (
+    "strided" if any(v) else "dense"))
+def test_glu_gradients_over_several_slabs_meet_the_fp32_sum_bound(dev, name, pads):
+    """G1-G3 of tests/conv1d_ref.py: the weight gradient in two to four position slabs (G2, G3: slab seams on sentence
+    seams, where the halo taps read zero and not the neighbouring sentence).  The gradient sums are compared with
+    float64 sums of the device's own dz (read back once it has passed the dz check of the test above), under the
+    summation bounds of tests/conv1d_ref.py; the workspace holds NaN before every call."""
+    from neuralmonkey_amd import ops
+    (bsz, steps, c, width), _, slices, per, last = R.GLU_SLAB_CASES[name]
+    px, py, pdy, pdx = pads
+    plan = R.slab_plan(bsz, steps, c, R.glu_filters(c, width))
+    assert (plan["slices"], plan["per"], plan["last"]) == (slices, per, last)
+    assert ops.conv1d_glu_workspace_floats(bsz, steps, c, width) * 4 == plan["bytes"]
+    g = torch.Generator().manual_seed(13 + int(name[1:]))
+    x = torch.randn(bsz, steps, c, generator=g, dtype=torch.float64)
+    w = torch.randn(width, c, 2 * c, generator=g, dtype=torch.float64) * math.sqrt(4.0 / c) / math.sqrt(width)
+    b = torch.randn(2 * c, generator=g, dtype=torch.float64) * 0.3
+    dy = torch.randn(bsz, steps, c, generator=g, dtype=torch.float64)
+    f32 = lambda t: t.float().contiguous().to(dev)
+    x_full, xd = _padded((bsz, steps, c), px, dev)
+    xd.copy_(x.float())
+    dy_full, dyd = _padded((bsz, steps, c), pdy, dev)
+    dyd.copy_(dy.float())
+    wd, bd = f32(w), f32(b)
+    x, w, b, dy = xd.double().cpu(), wd.double().cpu(), bd.double().cpu(), dyd.double().cpu()   # the rounded operands
+
+    y_full, y = _padded((bsz, steps, c), py, dev)
+    lin = torch.full((bsz * steps, c), float("nan"), device=dev)
+    sig = torch.full((bsz * steps, c), float("nan"), device=dev)
+    ops.conv1d_glu_fwd(xd, wd, bd, y, lin, sig, algo=0)
+    torch.cuda.synchronize()
+    z = _pre(x, w, b)
+    ref_lin, ref_sig = z[..., :c], torch.sigmoid(z[..., c:])
+    z_abs = _pre(x.abs(), w.abs(), b.abs())
+    _within(y, ref_lin * ref_sig + x, z_abs[..., :c] + x.abs(), "y")
+    _within(lin.view(bsz, steps, c), ref_lin, z_abs[..., :c], "lin_save")
+    _within(sig.view(bsz, steps, c), ref_sig, 0.25 * z_abs[..., c:], "sig_save")
+    ref_dz = torch.cat([dy * ref_sig, dy * ref_lin * ref_sig * (1 - ref_sig)], -1)
+    s_dz = torch.cat([dy.abs(), dy.abs() * z_abs[..., :c] * 0.25], -1)
+
+    def run(accumulate, algo):
+        dz = torch.full((bsz * steps, 2 * c), float("nan"), device=dev)
+        start = (0.5, 0.125, 0.25) if accumulate else (float("nan"),) * 3
+        dx_full, dx = _padded((bsz, steps, c), pdx, dev)
+        dx.fill_(start[0])
+        dw = torch.full_like(wd, start[1])
+        db = torch.full_like(bd, start[2])
+        wsp = torch.full((plan["bytes"] // 4,), float("nan"), device=dev)
+        ops.conv1d_glu_bwd(xd, wd, lin, sig, dyd, dz, dx=dx, accumulate_dx=accumulate, dfilt=dw, dbias=db,
+                           accumulate_params=accumulate, workspace=wsp, algo=algo)
+        torch.cuda.synchronize()
+        return dz, dx_full, dx, dw, db
+    first = run(False, 0)
+    _within(first[0].view(bsz, steps, 2 * c), ref_dz, s_dz, "dz")
+    dz = first[0].double().cpu().view(bsz, steps, 2 * c)                  # the operand of every gradient sum
+    assert all(bool((t > 0).any()) and bool((t < 0).any()) for t in (dz, x, w, dy))
+    filters = R.glu_filters(c, width)
+    want = (dy + _ref_conv_t(dz, [w], filters), _ref_wgrad(x, dz, width), dz.sum((0, 1)))
+    mags = (dy.abs() + _ref_conv_t(dz.abs(), [w.abs()], filters), _ref_wgrad(x.abs(), dz.abs(), width),
+            dz.abs().sum((0, 1)))
+    ks = (width * 2 * c + 1, bsz * steps + slices, bsz * steps + 16)    # (dx: every tap and filter, and the residual dy)
+
+    def check(out, accumulate, algo):
+        tag = "" if algo == 0 else " (scalar)"
+        label = "{}{} algo {} acc {}".format(name, " strided" if any(pads) else "", algo, int(accumulate))
+        assert torch.equal(out[0], first[0])                               # one dz kernel, the same saves
+        starts = (0.5, 0.125, 0.25) if accumulate else (0.0, 0.0, 0.0)
+        for got, ref, mag, k, start, what in zip(out[2:], want, mags, ks, starts, ("dx", "dW", "dbias")):
+            R.within(got, ref + start, k + int(accumulate), mag + start, label + " " + what, "glu " + what + tag)
+        if pdx:
+            assert bool((out[1][:, :, c:] == 7.0).all())
+    check(first, False, 0)
+    accumulated = run(True, 0)
+    check(accumulated, True, 0)
+    again = run(True, 0)
+    assert all(torch.equal(p, q) for p, q in zip(accumulated, again))
+    for accumulate in (False, True):
+        check(run(accumulate, 2), accumulate, 2)
+    for full, pad in ((x_full, px), (dy_full, pdy), (y_full, py)):
+        assert not pad or bool((full[:, :, c:] == 7.0).all())
+
+
 def test_forced_mfma_equals_auto_and_scalar_agrees(dev):
     """algo 1 is what auto takes for w <= 8 (bit-equal); the scalar kernel computes the same layer."""
     from neuralmonkey_amd import ops
@@ -225,11 +303,14 @@ def test_taped_encoder_functions_match_float64_autograd(dev):
 # entry point of include/nmhip_convs2s.h -> the tests of this file that call it
 ENTRY_POINTS = {
     "nm_conv1d_glu_fwd": ["test_glu_layer_forward_and_gradients_match_float64",
+                          "test_glu_gradients_over_several_slabs_meet_the_fp32_sum_bound",
                           "test_forced_mfma_equals_auto_and_scalar_agrees",
                           "test_taped_encoder_functions_match_float64_autograd"],
     "nm_conv1d_glu_workspace_bytes": ["test_glu_layer_forward_and_gradients_match_float64",
+                                      "test_glu_gradients_over_several_slabs_meet_the_fp32_sum_bound",
                                       "test_taped_encoder_functions_match_float64_autograd"],
     "nm_conv1d_glu_bwd": ["test_glu_layer_forward_and_gradients_match_float64",
+                          "test_glu_gradients_over_several_slabs_meet_the_fp32_sum_bound",
                           "test_taped_encoder_functions_match_float64_autograd"],
 }
 

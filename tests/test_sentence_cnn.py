@@ -1,6 +1,7 @@
 """SentenceCNNEncoder without a GPU: the reference's own constructor test runs against the product, the constructor
 has the reference's parameters, tests/small_sent_cnn.ini loads byte for byte from its bundle and declares the
-variables the reference's graph holds, and the new C entry points refuse bad arguments before any launch."""
+variables the reference's graph holds, the new C entry points refuse bad arguments before any launch, and the weight
+gradient's slab plan is the one the GPU cases of tests/conv1d_ref.py name."""
 import ctypes
 import os
 import tarfile
@@ -165,3 +166,57 @@ def test_conv_entry_points_validate_before_any_launch(lib):
     assert rc < 0 and b"nm_highway_fwd" in lib.nm_last_error()
     rc = lib.nm_highway_bwd(None, buf, buf, 4, buf, buf, buf, buf, 2, buf, 2, 4, 0)
     assert rc < 0 and b"bad shape" in lib.nm_last_error()
+
+
+def _tables(filters):
+    n = len(filters)
+    return (ctypes.c_int * n)(*[w for w, _ in filters]), (ctypes.c_int * n)(*[c for _, c in filters])
+
+
+# the largest shape of tests/test_sentence_cnn_gpu.py's first table: one slab, like every shape of that table
+LARGEST_ONE_SLAB_CASE = (2, 250, 128, [(2, 13), (7, 300)])
+
+
+def test_the_slab_plan_of_the_weight_gradient_is_the_one_the_gpu_cases_claim(lib):
+    """nm_conv1d_wgrad_workspace_bytes == slices * slab * 4 with the slab counts tests/conv1d_ref.py's table names: the
+    GPU cases P1-P6 cross the thresholds they say they cross, and the older cases never did."""
+    from .conv1d_ref import POOL_SLAB_CASES, slab_plan
+    for name, ((bsz, slen, e, filters), tiles, slices, per, last) in POOL_SLAB_CASES.items():
+        plan = slab_plan(bsz, slen, e, filters)
+        assert (plan["tiles"], plan["slices"], plan["per"], plan["last"]) == (tiles, slices, per, last), (name, plan)
+        widths, counts = _tables(filters)
+        slab = sum(w * e * n for w, n in filters)
+        assert lib.nm_conv1d_wgrad_workspace_bytes(bsz, slen, e, len(filters), widths, counts) == slices * slab * 4, name
+    limits = {name: slab_plan(*case[0])["limit"] for name, case in POOL_SLAB_CASES.items()}
+    assert limits == {"P1": "positions", "P2": "positions", "P3": "tiles", "P4": "cap", "P5": "positions",
+                      "P6": "positions"}
+    assert POOL_SLAB_CASES["P4"][4] % 32 != 0 and POOL_SLAB_CASES["P1"][3] % 32 != 0       # partial last LDS stages
+    assert POOL_SLAB_CASES["P2"][3] % POOL_SLAB_CASES["P2"][0][1] != 0                     # a seam mid-sentence
+    bsz, slen, e, filters = LARGEST_ONE_SLAB_CASE
+    widths, counts = _tables(filters)
+    assert slab_plan(bsz, slen, e, filters)["slices"] == 1
+    assert lib.nm_conv1d_wgrad_workspace_bytes(bsz, slen, e, 2, widths, counts) == (2 * 13 + 7 * 300) * 128 * 4
+
+
+def test_sixteen_filter_widths_are_accepted_and_seventeen_refused(lib):
+    from .conv1d_ref import W16
+    buf = (ctypes.c_float * 64)()
+    ibuf = (ctypes.c_int * 64)()
+    for nw in (16, 17):
+        filters = (W16 + [(1, 13)])[:nw]
+        widths, counts = _tables(filters)
+        ptrs = (ctypes.c_void_p * nw)(*[ctypes.addressof(buf)] * nw)
+        # a pooled width that is one short: the refusal that follows the width count's, so no launch either way
+        rc = lib.nm_conv1d_pool_fwd(None, buf, 11, 2, 6, 11, 5, nw, widths, counts, ptrs, ptrs, buf, ibuf, 13 * nw - 1,
+                                    None, None, None, None, 0)
+        assert rc < 0
+        nbytes = lib.nm_conv1d_wgrad_workspace_bytes(4, 2000, 11, nw, widths, counts)
+        if nw == 16:
+            assert b"sum of filter counts" in lib.nm_last_error()
+            assert nbytes == 29 * 72 * 11 * 13 * 4
+        else:
+            assert b"17 filter widths (1..16)" in lib.nm_last_error()
+            assert nbytes == 0
+        rc = lib.nm_conv1d_pool_bwd(None, buf, 11, 2, 6, 11, 5, nw, widths, counts, ptrs, buf, ibuf, buf, 13 * nw - 1,
+                                    buf, buf, 0, None, None, 1, None, 0, 0)
+        assert rc < 0 and (b"sum of filter counts" if nw == 16 else b"17 filter widths (1..16)") in lib.nm_last_error()
