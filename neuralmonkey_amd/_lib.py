@@ -274,6 +274,12 @@ VGG_SIGNATURES = {
     "nm_conv2d_act_fwd": (I, [P, P, L, L, L, L, L, P, L, L, I, P, I, P, L, I]),
 }
 
+# ... and every symbol include/nmhip_split.h declares (mask and lengths of SequenceSplitter's longer sequence, beside the
+# sentence-level heads in csrc/nm_pool.hip)
+SPLIT_SIGNATURES = {
+    "nm_split_mask": (I, [P, P, L, L, L, P, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -347,7 +353,8 @@ def load():
                               + list(GRU_SEQ_SIGNATURES.items()) + list(SUBWORD_SIGNATURES.items())
                               + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
                               + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
-                              + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())):
+                              + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
+                              + list(SPLIT_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,8 @@
 //                                the positions i / HB, i / HB + 256 / HB, ... -- the heads are the contiguous axis, so
 //                                a wave reads whole rows of energies; the reductions over T are LDS trees of fixed shape.
 //   sqerr_rows_kernel            one thread per row.
+//   split_mask_kernel            (include/nmhip_split.h) mask and lengths of model/sequence_split.py's longer sequence: one
+//                                wavefront per sentence.
 // No floating-point atomics anywhere: two runs are bit-equal.
 #include "nm_common.h"
 
@@ -295,6 +297,23 @@ __global__ __launch_bounds__(256) void sqerr_rows_kernel(float* p, long ld, long
     if (loss_rows != nullptr) loss_rows[r] = acc;
 }
 
+// One wavefront per sentence: lane i owns the positions i, i + 64, ...; each writes its mask entry `factor` times and the
+// wave sums the row (0/1 entries: exact in fp32 below 2^24 positions, which the entry point requires).
+__global__ __launch_bounds__(64) void split_mask_kernel(const float* __restrict__ mask, int T, int factor,
+                                                        float* __restrict__ out_mask, int32_t* __restrict__ lengths) {
+    const long b = blockIdx.x;
+    const float* row = mask + b * T;
+    float* out = out_mask + b * (long)T * factor;
+    float sum = 0.0f;
+    for (int t = threadIdx.x; t < T; t += 64) {
+        const float m = row[t];
+        sum += m;
+        for (int j = 0; j < factor; ++j) out[(long)t * factor + j] = m;
+    }
+    sum = nm_wave_sum(sum);
+    if (threadIdx.x == 0) lengths[b] = (int32_t)sum * factor;
+}
+
 bool pool_vec_ok(int64_t D, std::initializer_list<int64_t> lds, std::initializer_list<const void*> ptrs) {
     if (D % 4 != 0) return false;
     for (int64_t ld : lds)
@@ -427,6 +446,24 @@ int nm_sqerr_rows(void* stream, float* pred, int64_t ld, int64_t rows, int64_t d
     hipLaunchKernelGGL(sqerr_rows_kernel, dim3((unsigned)nm_cdiv(rows, 256)), dim3(256), 0, nm_stream(stream), pred,
                        (long)ld, (long)rows, (int)dim, targets, grad_scale, write_grad ? 1 : 0, loss_rows);
     NM_LAUNCH_CHECK("nm_sqerr_rows");
+}
+
+// include/nmhip_split.h
+int nm_split_mask(void* stream, const float* mask, int64_t B, int64_t T, int64_t factor, float* out_mask,
+                  int32_t* lengths) {
+    NM_REQUIRE(B >= 1 && T >= 1 && factor >= 1, "nm_split_mask: bad sizes B %lld, T %lld, factor %lld", (long long)B,
+               (long long)T, (long long)factor);
+    NM_REQUIRE(B < (1ll << 31) && T < (1ll << 24) && factor < (1ll << 24) && T * factor < (1ll << 31),
+               "nm_split_mask: sizes B %lld, T %lld, factor %lld beyond the grid or the exact fp32 row sum", (long long)B,
+               (long long)T, (long long)factor);
+    NM_REQUIRE(mask != nullptr && out_mask != nullptr && lengths != nullptr,
+               "nm_split_mask: null pointer (mask, out_mask or lengths)");
+    const float* in_end = mask + B * T;
+    const float* out_end = out_mask + B * T * factor;
+    NM_REQUIRE(out_end <= mask || in_end <= out_mask, "nm_split_mask: out_mask aliasing mask");
+    hipLaunchKernelGGL(split_mask_kernel, dim3((unsigned)B), dim3(64), 0, nm_stream(stream), mask, (int)T, (int)factor,
+                       out_mask, lengths);
+    NM_LAUNCH_CHECK("nm_split_mask");
 }
 
 }  // extern "C"

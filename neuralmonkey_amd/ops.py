@@ -1995,6 +1995,18 @@ def pool_bwd(mode, dout, mask, dx, x=None, out=None, ties=None, accumulate=False
     return dx
 
 
+def split_mask(mask, factor, out_mask, lengths):
+    """model/sequence_split.py: ``out_mask`` [B, T*factor] = every entry of ``mask`` [B, T] ``factor`` times, and
+    ``lengths`` [B] int32 = the row sums of ``mask`` times ``factor`` (include/nmhip_split.h), in one launch."""
+    bsz, steps = mask.shape
+    assert _f32(mask).is_contiguous() and mask.dim() == 2
+    assert tuple(_f32(out_mask).shape) == (bsz, steps * int(factor)) and out_mask.is_contiguous()
+    assert tuple(_i32(lengths).shape) == (bsz,) and lengths.is_contiguous()
+    _lib.check(_lib.load().nm_split_mask(_stream(), mask.data_ptr(), bsz, steps, int(factor), out_mask.data_ptr(),
+                                         lengths.data_ptr()), "nm_split_mask")
+    return out_mask, lengths
+
+
 def time_softmax_fwd(e, mask, w, s_out=None, z_out=None):
     """encoders/attentive.py:60-75 on energies [B, T, H], normalised along T: w = softmax_t(e) * mask, renormalised with
     1e-8 in the denominator (mask None: the plain softmax).  ``s_out`` [B, T, H] and ``z_out`` [B, H] are what
