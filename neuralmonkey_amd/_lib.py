@@ -280,6 +280,12 @@ SPLIT_SIGNATURES = {
     "nm_split_mask": (I, [P, P, L, L, L, P, P]),
 }
 
+# ... and every symbol include/nmhip_beam_wide.h declares (the beam step for 17 to 64 hypotheses, beside the narrow
+# beam steps in csrc/nm_logits.hip)
+BEAM_WIDE_SIGNATURES = {
+    "nm_beam_topk_step_wide": (I, [P, P, L, L, L, L, P, P, P, P, I, P, P, P, P, P, P, P, P, L, P, P, P, P, P, P, L]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -354,7 +360,7 @@ def load():
                               + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
                               + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
                               + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
-                              + list(SPLIT_SIGNATURES.items())):
+                              + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -7,6 +7,7 @@
 //                                           tf.nn.top_k over [B, k*V], div/mod, gathers
 #include "nm_common.h"
 #include "../../include/nmhip.h"
+#include "../../include/nmhip_beam_wide.h"
 #include <stdlib.h>
 
 #define NM_NEG_INF_F (-1e9f)   // the reference's INF (beam_search_decoder.py:42)
@@ -919,10 +920,7 @@ extern "C" int nm_gumbel_argmax(void* stream, const float* x, int64_t ldx, int64
     NM_LAUNCH_CHECK("nm_gumbel_argmax");
 }
 
-extern "C" int64_t nm_beam_workspace_bytes(int64_t B, int64_t k, int64_t V) {
-    (void)k; (void)V;
-    return B * 64 * BEAM_MAX_K * 8 + 256;
-}
+// nm_beam_workspace_bytes: with the wide entry's layout below; B * 64 * BEAM_MAX_K * 8 + 256 for every k <= 16
 
 extern "C" int nm_beam_topk_step(void* stream, const float* logits, int64_t ldx, int64_t B, int64_t k,
                                  int64_t V, const float* rmax, const float* rlse,
@@ -1287,6 +1285,417 @@ extern "C" int nm_beam_topk_step_tiles(void* stream, const float* logits, int64_
     else NM_TILES(16);
 #undef NM_TILES
     NM_LAUNCH_CHECK("nm_beam_topk_step_tiles");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Wide beams (k up to 64): nm_beam_topk_step_wide.  No per-thread candidate lists: the k best of a sentence's
+// k*V scores are found by counting.
+//   bin(score) = a monotone map of the score onto nbins integers, 1/scale wide, counted down from the sentence's
+//                best possible score `top` (the best row's score of its own maximum); scores further than
+//                nbins/scale below `top` share bin 0.  A higher bin means a strictly higher score.
+//   pass 1     workgroup (row, slice) streams its slice once, counts bins in LDS and leaves its highest
+//              bins, down to the one that holds its own k-th best, as (bin, count) pairs in the workspace (plain
+//              stores: nothing further down can hold the sentence's k-th best), with the highest bin it saw.
+//   select     one workgroup per sentence adds the lists up and finds T, the bin of the sentence's k-th best,
+//              and how many candidates sit at or above it.
+//   pass 2     the slices that reach T are read again; candidates at or above T go to the sentence's buffer as
+//              (order-preserving key of the score, flat index) through an integer cursor.
+//   final      one workgroup per sentence sorts the buffer in LDS by (key desc, flat index asc) -- a strict total
+//              order, so the arrival order in the buffer never shows -- and emits the first k with the derived
+//              search state.  When more candidates reach T than the buffer holds (uniform logits, the -1e9
+//              rows of a first step with V < k, thousands of equal maxima, or a k-th best further than
+//              nbins/scale below the top), the same workgroup streams the sentence's rows itself: candidates
+//              that beat the running k-th best are appended, and the buffer is sorted and cut back to k when
+//              it fills.  That selection is exact as well, only slower.
+// Outside that last path the logits are read once for the statistics (when they are not given), once by pass 1
+// and a third time only in the slices that reach T.
+// ---------------------------------------------------------------------------------------------
+#define WIDE_MAX_K 64
+#define WIDE_NT 256
+#define WIDE_MAX_BINS 2048
+#define WIDE_SORT 2048                      // LDS entries of the final sort; the candidate buffer holds at most this
+#define WIDE_HDR 16                         // ints: cursor, T, candidates >= T, overflow flag
+
+struct WideLayout {
+    int ns, per, nbins, cap;
+    float scale;
+    long stride, off_listn, off_smax, off_list, off_cand;      // in ints, per sentence
+};
+
+static inline WideLayout wide_layout(int64_t k, int64_t V) {
+    WideLayout L;
+    int64_t ns = (V + 8191) / 8192;
+    if (ns > 8) ns = 8;
+    if (k <= BEAM_MAX_K) {
+        // the narrow kernels' workspace (8192 bytes per sentence) has to do: 1024 bins, 4096 bytes of lists
+        L.nbins = 1024; L.cap = 384; L.scale = 16.0f;
+        const int64_t fit = 4096 / (k * k * 8);
+        if (ns > fit) ns = fit;
+    } else {
+        L.nbins = WIDE_MAX_BINS; L.cap = WIDE_SORT; L.scale = 32.0f;
+    }
+    if (ns < 1) ns = 1;
+    L.ns = (int)ns;
+    L.per = (int)((((V + ns - 1) / ns) + 3) & ~3L);            // multiple of 4: float4 loads stay aligned
+    const long nwg = (long)(k * ns);
+    L.off_listn = WIDE_HDR;
+    L.off_smax = L.off_listn + ((nwg + 1) & ~1L);
+    L.off_list = L.off_smax + ((nwg + 1) & ~1L);
+    L.off_cand = L.off_list + nwg * k * 2;
+    L.stride = L.off_cand + 2L * L.cap;
+    return L;
+}
+
+extern "C" int64_t nm_beam_workspace_bytes(int64_t B, int64_t k, int64_t V) {
+    if (k <= BEAM_MAX_K || k > WIDE_MAX_K || V <= 0) return B * 64 * BEAM_MAX_K * 8 + 256;
+    return B * wide_layout(k, V).stride * 4 + 256;
+}
+
+// order-preserving 32-bit key of a score (-0 ranks with +0, as the comparison of the floats has it)
+__device__ __forceinline__ unsigned wide_key(float s) {
+    unsigned u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float wide_unkey(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+// (key desc, flat index asc) as ONE descending 64-bit order; 0 is the padding, below every candidate
+__device__ __forceinline__ unsigned long long wide_comp(float s, int flat) {
+    return ((unsigned long long)wide_key(s) << 32) | (unsigned)(0x7fffffff - flat);
+}
+// subtraction, product with a positive constant, clamps and truncation are all monotone: bin(a) > bin(b) => a > b
+__device__ __forceinline__ int wide_bin(float top, float s, int nbins, float scale) {
+    const float d = fminf(fmaxf((top - s) * scale, 0.0f), (float)(nbins - 1));
+    return nbins - 1 - (int)d;
+}
+
+// the best score any candidate of sentence b can have: max over its rows of the score of the row's own maximum
+// (x - max = 0).  Every workgroup of a sentence derives the same value from the same inputs.  Ends with a barrier.
+__device__ __forceinline__ float wide_sentence_top(int b, int k, const float* __restrict__ rlse,
+                                                   const float* __restrict__ logprob_sum,
+                                                   const int* __restrict__ lengths, const int* __restrict__ finished,
+                                                   const float* __restrict__ penalty, float* sh) {
+    if (threadIdx.x < 64) {
+        float best = -INFINITY;
+        if ((int)threadIdx.x < k) {
+            const int r = b * k + threadIdx.x;
+            const int fin = finished[r];
+            const float lp = fin ? 0.0f : (0.0f - rlse[r]);
+            best = (logprob_sum[r] + lp) / penalty[lengths[r] + 1 - (fin ? 1 : 0)];
+        }
+        best = nm_wave_max(best);
+        if (threadIdx.x == 0) *sh = best;
+    }
+    __syncthreads();
+    return *sh;
+}
+
+// suffix counts over the block: thread t receives the sum of `mine` over the threads above it
+template <int NT>
+__device__ __forceinline__ int wide_count_above(int mine, int* scan) {
+    const int t = threadIdx.x;
+    scan[t] = mine;
+    __syncthreads();
+    for (int off = 1; off < NT; off <<= 1) {
+        const int v = scan[t] + (t + off < NT ? scan[t + off] : 0);
+        __syncthreads();
+        scan[t] = v;
+        __syncthreads();
+    }
+    return scan[t] - mine;
+}
+
+// f(x, v) for every element of columns [beg, end) of a row, float4 loads where the row allows
+template <typename F>
+__device__ __forceinline__ void wide_visit(const float* __restrict__ row, long ldx, int beg, int end, F f) {
+    const int tid = threadIdx.x;
+    if (end <= beg) return;
+    if ((ldx & 3) == 0 && nm_aligned16_dev(row)) {
+        const int end4 = beg + ((end - beg) & ~3);
+        for (int v = beg + tid * 4; v < end4; v += WIDE_NT * 4) {
+            const float4 x = *reinterpret_cast<const float4*>(row + v);
+            f(x.x, v); f(x.y, v + 1); f(x.z, v + 2); f(x.w, v + 3);
+        }
+        for (int v = end4 + tid; v < end; v += WIDE_NT) f(row[v], v);
+    } else {
+        for (int v = beg + tid; v < end; v += WIDE_NT) f(row[v], v);
+    }
+}
+
+struct WideArgs {
+    const float* logits; long ldx; int V, k;
+    const float *rmax, *rlse, *logprob_sum; const int *lengths, *finished; const float* penalty;
+    int* ws; WideLayout L;
+};
+
+__global__ __launch_bounds__(WIDE_NT) void wide_hist_kernel(WideArgs a) {
+    __shared__ int hist[WIDE_MAX_BINS];
+    __shared__ int scan[WIDE_NT];
+    __shared__ float shtop;
+    __shared__ int list_n, smax_s;
+    const int tid = threadIdx.x, ns = a.L.ns, k = a.k, V = a.V, nbins = a.L.nbins;
+    const int r = blockIdx.x / ns, slice = blockIdx.x - r * ns, b = r / k, j = r - b * k;
+    int* sws = a.ws + (long)b * a.L.stride;
+    const int w = j * ns + slice;
+    const float top = wide_sentence_top(b, k, a.rlse, a.logprob_sum, a.lengths, a.finished, a.penalty, &shtop);
+    for (int i = tid; i < nbins; i += WIDE_NT) hist[i] = 0;
+    if (tid == 0) { list_n = 0; smax_s = -1; }
+    __syncthreads();
+    const int fin = a.finished[r];
+    const float lps = a.logprob_sum[r], scale = a.L.scale;
+    const float pen = a.penalty[a.lengths[r] + 1 - (fin ? 1 : 0)];
+    if (fin) {
+        // lp = 0 at <pad>, -1e9 elsewhere (:444-456): two distinct scores, no logits read
+        if (slice == 0 && tid == 0) {
+            hist[wide_bin(top, (lps + 0.0f) / pen, nbins, scale)] += 1;
+            if (V > 1) hist[wide_bin(top, (lps + NM_NEG_INF_F) / pen, nbins, scale)] += V - 1;
+        }
+    } else {
+        const float mx = a.rmax[r], lse = a.rlse[r];
+        const int beg = slice * a.L.per, end = min(V, beg + a.L.per);
+        wide_visit(a.logits + (long)r * a.ldx, a.ldx, beg, end, [&](float x, int) {
+            atomicAdd(&hist[wide_bin(top, (lps + ((x - mx) - lse)) / pen, nbins, scale)], 1);
+        });
+    }
+    __syncthreads();
+    // thread t owns bins [t*C, (t+1)*C): from the top down, a non-empty bin is listed while fewer than k
+    // candidates of this slice lie above it
+    const int C = nbins / WIDE_NT;
+    int mine = 0;
+    for (int c = 0; c < C; ++c) mine += hist[tid * C + c];
+    int above = wide_count_above<WIDE_NT>(mine, scan);
+    int* list = sws + a.L.off_list + (long)w * k * 2;
+    for (int c = C - 1; c >= 0; --c) {
+        const int bin = tid * C + c, cnt = hist[bin];
+        if (cnt > 0) {
+            if (above < k) {
+                const int slot = atomicAdd(&list_n, 1);
+                if (slot < k) { list[2 * slot] = bin; list[2 * slot + 1] = cnt; }
+            }
+            atomicMax(&smax_s, bin);
+            above += cnt;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sws[a.L.off_listn + w] = min(list_n, k);
+        sws[a.L.off_smax + w] = smax_s;
+    }
+}
+
+__global__ __launch_bounds__(WIDE_NT) void wide_select_kernel(int* ws, WideLayout L, int k) {
+    __shared__ int hist[WIDE_MAX_BINS];
+    __shared__ int scan[WIDE_NT];
+    const int tid = threadIdx.x, nbins = L.nbins, nwg = k * L.ns;
+    int* sws = ws + (long)blockIdx.x * L.stride;
+    __shared__ int res[3];
+    for (int i = tid; i < nbins; i += WIDE_NT) hist[i] = 0;
+    if (tid == 0) { res[0] = 0; res[1] = 0x7fffffff; res[2] = 1; }       // until a T is found: the exact path
+    __syncthreads();
+    for (int e = tid; e < nwg * k; e += WIDE_NT) {
+        const int w = e / k, i = e - w * k;
+        if (i < sws[L.off_listn + w]) {
+            const int bin = sws[L.off_list + 2L * e], cnt = sws[L.off_list + 2L * e + 1];
+            if (bin >= 0 && bin < nbins) atomicAdd(&hist[bin], cnt);
+        }
+    }
+    __syncthreads();
+    const int C = nbins / WIDE_NT;
+    int mine = 0;
+    for (int c = 0; c < C; ++c) mine += hist[tid * C + c];
+    int above = wide_count_above<WIDE_NT>(mine, scan);
+    for (int c = C - 1; c >= 0; --c) {
+        const int bin = tid * C + c, cnt = hist[bin];
+        if (above < k && above + cnt >= k) {               // the bin of the k-th best: one thread finds it
+            res[0] = bin;
+            res[1] = above + cnt;
+            res[2] = (above + cnt > L.cap) ? 1 : 0;
+        }
+        above += cnt;
+    }
+    __syncthreads();
+    if (tid == 0) { sws[0] = 0; sws[1] = res[0]; sws[2] = res[1]; sws[3] = res[2]; }    // cursor back to zero
+}
+
+__global__ __launch_bounds__(WIDE_NT) void wide_collect_kernel(WideArgs a) {
+    __shared__ float shtop;
+    const int tid = threadIdx.x, ns = a.L.ns, k = a.k, V = a.V, nbins = a.L.nbins, cap = a.L.cap;
+    const int r = blockIdx.x / ns, slice = blockIdx.x - r * ns, b = r / k, j = r - b * k;
+    int* sws = a.ws + (long)b * a.L.stride;
+    const int T = sws[1];
+    if (sws[3] || sws[a.L.off_smax + j * ns + slice] < T) return;      // the same for the whole workgroup
+    const float top = wide_sentence_top(b, k, a.rlse, a.logprob_sum, a.lengths, a.finished, a.penalty, &shtop);
+    const int fin = a.finished[r];
+    const float lps = a.logprob_sum[r], scale = a.L.scale;
+    const float pen = a.penalty[a.lengths[r] + 1 - (fin ? 1 : 0)];
+    int* cand = sws + a.L.off_cand;
+    const int base = j * V;
+    auto offer = [&](float s, int v) {
+        if (wide_bin(top, s, nbins, scale) >= T) {
+            const int slot = atomicAdd(&sws[0], 1);
+            if (slot < cap) { cand[2 * slot] = (int)wide_key(s); cand[2 * slot + 1] = base + v; }
+        }
+    };
+    if (fin) {
+        // <pad>, then the lowest words of the tie at -1e9: no more than k of those can be selected
+        if (slice == 0 && tid < V && tid <= k) offer((lps + (tid == 0 ? 0.0f : NM_NEG_INF_F)) / pen, tid);
+    } else {
+        const float mx = a.rmax[r], lse = a.rlse[r];
+        const int beg = slice * a.L.per, end = min(V, beg + a.L.per);
+        wide_visit(a.logits + (long)r * a.ldx, a.ldx, beg, end,
+                   [&](float x, int v) { offer((lps + ((x - mx) - lse)) / pen, v); });
+    }
+}
+
+// bitonic sort of buf[0, P) into descending order, P a power of two, by the whole block
+__device__ __forceinline__ void wide_sort_desc(unsigned long long* buf, int P) {
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
+                const int i = 2 * t - (t & (stride - 1)), jj = i + stride;
+                const bool desc = (i & size) == 0 || size == P;
+                const unsigned long long x = buf[i], y = buf[jj];
+                if (desc ? x < y : x > y) { buf[i] = y; buf[jj] = x; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void wide_final_kernel(WideArgs a, int end_id, float* __restrict__ out_score,
+                                                          int* __restrict__ out_word, int* __restrict__ out_beam,
+                                                          float* __restrict__ out_logprob_sum,
+                                                          int* __restrict__ out_lengths, int* __restrict__ out_finished,
+                                                          int* __restrict__ out_src_row, int* __restrict__ all_finished) {
+    __shared__ unsigned long long buf[WIDE_SORT];
+    __shared__ int nbuf;
+    __shared__ unsigned long long thr_s;
+    const int tid = threadIdx.x, b = blockIdx.x, k = a.k, V = a.V;
+    const int* sws = a.ws + (long)b * a.L.stride;
+    if (!sws[3]) {
+        const int n = min(sws[0], a.L.cap);
+        int P = WIDE_MAX_K;                                  // the k emitted entries are always initialised
+        while (P < n) P <<= 1;
+        const int* cand = sws + a.L.off_cand;
+        for (int i = tid; i < P; i += 1024)
+            buf[i] = i < n ? (((unsigned long long)(unsigned)cand[2 * i] << 32) | (unsigned)(0x7fffffff - cand[2 * i + 1]))
+                           : 0ull;
+        __syncthreads();
+        wide_sort_desc(buf, P);
+    } else {
+        // the exact path for buffers that overflow: stream the sentence, keep what beats the running k-th best
+        if (tid == 0) nbuf = 0;
+        unsigned long long thr = 0ull;
+        __syncthreads();
+        for (int j = 0; j < k; ++j) {
+            const int r = b * k + j;
+            const int fin = a.finished[r];
+            const float lps = a.logprob_sum[r], mx = a.rmax[r], lse = a.rlse[r];
+            const float pen = a.penalty[a.lengths[r] + 1 - (fin ? 1 : 0)];
+            const int vend = fin ? min(V, k + 1) : V;
+            const float* row = a.logits + (long)r * a.ldx;
+            for (int v0 = 0; v0 < vend; v0 += 1024) {
+                const int v = v0 + tid;
+                if (v < vend) {
+                    const float lp = fin ? (v == 0 ? 0.0f : NM_NEG_INF_F) : ((row[v] - mx) - lse);
+                    const unsigned long long c = wide_comp((lps + lp) / pen, j * V + v);
+                    if (c > thr) buf[atomicAdd(&nbuf, 1)] = c;          // nbuf <= 1024 before the chunk
+                }
+                __syncthreads();
+                const int n = nbuf;
+                __syncthreads();                                        // everyone has read it before the next append
+                if (n > WIDE_SORT - 1024) {
+                    for (int i = n + tid; i < WIDE_SORT; i += 1024) buf[i] = 0ull;
+                    __syncthreads();
+                    wide_sort_desc(buf, WIDE_SORT);
+                    if (tid == 0) { nbuf = k; thr_s = buf[k - 1]; }
+                    __syncthreads();
+                    thr = thr_s;
+                }
+            }
+        }
+        const int n = nbuf;
+        for (int i = n + tid; i < WIDE_SORT; i += 1024) buf[i] = 0ull;
+        __syncthreads();
+        wide_sort_desc(buf, WIDE_SORT);
+    }
+    if (tid < k) {
+        const unsigned long long c = buf[tid];
+        long flat = 0x7fffffffL - (long)(unsigned)(c & 0xffffffffull);
+        flat = flat < 0 ? 0 : (flat >= (long)k * V ? (long)k * V - 1 : flat);
+        const int j = (int)(flat / V), v = (int)(flat - (long)j * V);
+        const int r = b * k + j;
+        const int fin = a.finished[r];
+        const float lp = fin ? (v == 0 ? 0.0f : NM_NEG_INF_F) : ((a.logits[(long)r * a.ldx + v] - a.rmax[r]) - a.rlse[r]);
+        const int o = b * k + tid;
+        out_score[o] = wide_unkey((unsigned)(c >> 32));
+        out_word[o] = v;
+        out_beam[o] = j;
+        out_logprob_sum[o] = a.logprob_sum[r] + lp;
+        out_lengths[o] = a.lengths[r] + 1 - (fin ? 1 : 0);
+        const int nf = fin | (v == end_id);
+        out_finished[o] = nf;
+        out_src_row[o] = r;
+        if (all_finished && !nf) *all_finished = 0;     // plain store, see nm_greedy_update
+    }
+}
+
+// max / lse of every row from the tile records of nm_logits_stats_gemm
+__global__ __launch_bounds__(256) void wide_tile_stats_kernel(const float4* __restrict__ stats, int ntiles,
+                                                              float* __restrict__ max_out, float* __restrict__ lse_out) {
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int r = blockIdx.x;
+    float M, lse;
+    int A;
+    merge_row_tiles<256>(stats + (long)r * ntiles, ntiles, M, A, lse, shf, shi);
+    if (threadIdx.x == 0) { max_out[r] = M; lse_out[r] = lse; }
+}
+
+extern "C" int nm_beam_topk_step_wide(void* stream, const float* logits, int64_t ldx, int64_t B, int64_t k, int64_t V,
+                                      const float* logprob_sum, const int32_t* lengths, const int32_t* finished,
+                                      const float* penalty, int end_id, float* out_score, int32_t* out_word,
+                                      int32_t* out_beam, float* out_logprob_sum, int32_t* out_lengths,
+                                      int32_t* out_finished, int32_t* out_src_row, void* workspace,
+                                      int64_t workspace_bytes, int32_t* all_finished, float* rmax_out, float* rlse_out,
+                                      const float* rmax_in, const float* rlse_in, const float* stats, int64_t tile_w) {
+    NM_REQUIRE(logits && logprob_sum && lengths && finished && penalty && out_score && out_word && out_beam &&
+                   out_logprob_sum && out_lengths && out_finished && out_src_row && workspace,
+               "nm_beam_topk_step_wide: null pointer");
+    NM_REQUIRE(B > 0 && k >= 1 && k <= WIDE_MAX_K && V > 0 && k * V < (1L << 31) && ldx >= V,
+               "nm_beam_topk_step_wide: bad shape B=%ld k=%ld V=%ld ldx=%ld (1 <= k <= 64, k*V < 2^31, ldx >= V)",
+               (long)B, (long)k, (long)V, (long)ldx);
+    NM_REQUIRE((rmax_in != nullptr) == (rlse_in != nullptr), "nm_beam_topk_step_wide: rmax_in and rlse_in go together");
+    NM_REQUIRE(!(rmax_in && stats), "nm_beam_topk_step_wide: given row statistics and tile statistics exclude each other");
+    NM_REQUIRE(rmax_in || (rmax_out && rlse_out), "nm_beam_topk_step_wide: computed statistics need rmax_out / rlse_out");
+    NM_REQUIRE(!stats || ((tile_w == 64 || tile_w == 128) && nm_aligned16(stats)),
+               "nm_beam_topk_step_wide: tile width %ld (nm_logits_stats_tile gives 64 or 128)", (long)tile_w);
+    NM_REQUIRE(workspace_bytes >= nm_beam_workspace_bytes(B, k, V), "nm_beam_topk_step_wide: workspace too small");
+    NM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3u) == 0, "nm_beam_topk_step_wide: workspace must be 4-byte aligned");
+    WideArgs a;
+    a.L = wide_layout(k, V);
+    NM_REQUIRE(B * a.L.stride * 4 <= workspace_bytes && B * k * a.L.ns < (1L << 31),
+               "nm_beam_topk_step_wide: too many hypothesis rows");
+    hipStream_t st = nm_stream(stream);
+    const unsigned rows = (unsigned)(B * k);
+    if (stats)
+        hipLaunchKernelGGL(wide_tile_stats_kernel, dim3(rows), dim3(256), 0, st, reinterpret_cast<const float4*>(stats),
+                           (int)((V + tile_w - 1) / tile_w), rmax_out, rlse_out);
+    else if (!rmax_in)
+        hipLaunchKernelGGL((row_stats_kernel<1024>), dim3(rows), dim3(1024), 0, st, logits, (long)ldx, (int)V, rmax_out,
+                           rlse_out, (int*)nullptr);
+    a.logits = logits; a.ldx = (long)ldx; a.V = (int)V; a.k = (int)k;
+    a.rmax = rmax_in ? rmax_in : rmax_out; a.rlse = rlse_in ? rlse_in : rlse_out;
+    a.logprob_sum = logprob_sum; a.lengths = lengths; a.finished = finished; a.penalty = penalty;
+    a.ws = reinterpret_cast<int*>(workspace);
+    const unsigned nwg = rows * (unsigned)a.L.ns;
+    hipLaunchKernelGGL(wide_hist_kernel, dim3(nwg), dim3(WIDE_NT), 0, st, a);
+    hipLaunchKernelGGL(wide_select_kernel, dim3((unsigned)B), dim3(WIDE_NT), 0, st, a.ws, a.L, (int)k);
+    hipLaunchKernelGGL(wide_collect_kernel, dim3(nwg), dim3(WIDE_NT), 0, st, a);
+    hipLaunchKernelGGL(wide_final_kernel, dim3((unsigned)B), dim3(1024), 0, st, a, end_id, out_score, out_word, out_beam,
+                       out_logprob_sum, out_lengths, out_finished, out_src_row, all_finished);
+    NM_LAUNCH_CHECK("nm_beam_topk_step_wide");
 }
 
 // ---------------------------------------------------------------------------

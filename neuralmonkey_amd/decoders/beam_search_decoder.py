@@ -27,6 +27,9 @@ from .autoregressive import AutoregressiveDecoder, DecoderFeedables, LoopState
 from .decoder import CHECK_EVERY, CHECK_EVERY_BEAM
 
 INF = 1e9
+NARROW_BEAM_SIZE = 16     # up to here: the register-list kernels (nm_beam_topk_step, _fused, _tiles)
+MAX_BEAM_SIZE = 64        # above, up to here: the counting kernel (nm_beam_topk_step_wide); the attention
+                          # entries' rows_per_key <= 64 is the next bound
 
 
 class SearchState(NamedTuple):
@@ -66,9 +69,9 @@ class BeamSearchDecoder(ModelPart):
         self.length_normalization = length_normalization
         self.max_steps_int = max_steps
         self.max_steps = Placeholder("{}/max_steps".format(name), default=max_steps)
-        if beam_size < 1 or beam_size > 16:
-            raise ValueError("beam_size must be between 1 and 16 for the HIP top-k kernels, was {}"
-                             .format(beam_size))
+        if beam_size < 1 or beam_size > MAX_BEAM_SIZE:
+            raise ValueError("beam_size must be between 1 and {} for the HIP top-k kernels, was {}"
+                             .format(MAX_BEAM_SIZE, beam_size))
         if not hasattr(parent_decoder, "make_stepper"):
             raise NotImplementedError("BeamSearchDecoder: parent decoder '{}' has no stepwise inference "
                                       "interface (make_stepper)".format(type(parent_decoder).__name__))
@@ -198,9 +201,14 @@ class BeamSearchDecoder(ModelPart):
         steps = executed = 0
         while steps < max_steps:
             cur, nxt = steps & 1, (steps & 1) ^ 1
-            ops.beam_topk_step(ens, bsz, k, zero_stat, zero_stat, lps[cur], lens[cur], fin[cur], penalty,
-                               END_TOKEN_INDEX, scores, word, beam, lps[nxt], lens[nxt], fin[nxt], src, ws,
-                               allfin[steps:steps + 1])
+            if k > NARROW_BEAM_SIZE:
+                ops.beam_topk_step_wide(ens, bsz, k, lps[cur], lens[cur], fin[cur], penalty, END_TOKEN_INDEX, scores,
+                                        word, beam, lps[nxt], lens[nxt], fin[nxt], src, ws,
+                                        all_finished=allfin[steps:steps + 1], rmax_in=zero_stat, rlse_in=zero_stat)
+            else:
+                ops.beam_topk_step(ens, bsz, k, zero_stat, zero_stat, lps[cur], lens[cur], fin[cur], penalty,
+                                   END_TOKEN_INDEX, scores, word, beam, lps[nxt], lens[nxt], fin[nxt], src, ws,
+                                   allfin[steps:steps + 1])
             ops.beam_reorder_tokens(tok[cur], srcf, wordf, tok[nxt], steps + 1, rows)
             for mod in models:
                 mod["stepper"].reorder(srcf)
@@ -323,7 +331,11 @@ class BeamSearchDecoder(ModelPart):
             cur, nxt = s & 1, (s & 1) ^ 1
             srcf, wordf = src_hist[s], word_hist[s]       # this body's selections ARE the history records
             src, word = srcf.view(bsz, k), wordf.view(bsz, k)
-            if use_stats:
+            if k > NARROW_BEAM_SIZE:                      # counting selection: no per-thread candidate lists
+                ops.beam_topk_step_wide(logits, bsz, k, lps[cur], lens[cur], fin[cur], penalty, END_TOKEN_INDEX,
+                                        scores, word, beam, lps[nxt], lens[nxt], fin[nxt], src, ws, rmax, rlse,
+                                        allfin[s:s + 1], stats=stats if use_stats else None)
+            elif use_stats:
                 ops.beam_topk_step_tiles(logits, stats, bsz, k, lps[cur], lens[cur], fin[cur], penalty,
                                          END_TOKEN_INDEX, scores, word, beam, lps[nxt], lens[nxt], fin[nxt], src, ws,
                                          rmax, rlse, allfin[s:s + 1])

@@ -512,6 +512,24 @@ def beam_topk_step_tiles(logits, stats, b, k, logprob_sum, lengths, finished, pe
         workspace.numel() * 4, _p(all_finished), rmax.data_ptr(), rlse.data_ptr()), "nm_beam_topk_step_tiles")
 
 
+def beam_topk_step_wide(logits, b, k, logprob_sum, lengths, finished, penalty, end_id, out_score, out_word, out_beam,
+                        out_logprob_sum, out_lengths, out_finished, out_src_row, workspace, rmax=None, rlse=None,
+                        all_finished=None, rmax_in=None, rlse_in=None, stats=None, tile=None):
+    """One beam body for beams of up to 64 hypotheses.  Row statistics: ``rmax_in`` / ``rlse_in`` when given (the
+    two-pass and ensemble convention), else the tile statistics ``stats`` of ``logits_stats_gemm``, else computed;
+    in the last two cases they are left in ``rmax`` / ``rlse``."""
+    lib = _lib.load()
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == b * k
+    if stats is not None and tile is None:
+        tile = lib.nm_logits_stats_tile(b * k)
+    _lib.check(lib.nm_beam_topk_step_wide(
+        _stream(), logits.data_ptr(), logits.stride(0), b, k, logits.shape[1], logprob_sum.data_ptr(),
+        lengths.data_ptr(), finished.data_ptr(), penalty.data_ptr(), end_id, _p(out_score), _p(out_word),
+        _p(out_beam), _p(out_logprob_sum), _p(out_lengths), _p(out_finished), _p(out_src_row), _p(workspace),
+        0 if workspace is None else workspace.numel() * workspace.element_size(), _p(all_finished), _p(rmax), _p(rlse),
+        _p(rmax_in), _p(rlse_in), _p(stats), tile or 0), "nm_beam_topk_step_wide")
+
+
 def attn_partials_layout(rows, s, a, c):
     """(nchunk, pctx offset, pstat offset) in floats inside the attention workspace, or None when the shape is
     served by the any-shape kernel (no split-S partials)."""
