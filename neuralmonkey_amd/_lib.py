@@ -286,6 +286,13 @@ BEAM_WIDE_SIGNATURES = {
     "nm_beam_topk_step_wide": (I, [P, P, L, L, L, L, P, P, P, P, I, P, P, P, P, P, P, P, P, L, P, P, P, P, P, P, L]),
 }
 
+# ... and every symbol include/nmhip_sample.h declares (the truncated sampling step of SamplingDecoder: temperature,
+# top-k and nucleus sampling, csrc/nm_sample.hip)
+SAMPLE_SIGNATURES = {
+    "nm_sample_step": (I, [P, P, L, L, L, F, L, F, P, ctypes.c_uint32, I, P, P, P, P, P, P, P, P, P, P, P, L]),
+    "nm_sample_lds_max_columns": (L, []),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -360,7 +367,8 @@ def load():
                               + list(BNSYNC_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())
                               + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
                               + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
-                              + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())):
+                              + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())
+                              + list(SAMPLE_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,6 @@
 from .decoder import Decoder                             # noqa: F401
 from .beam_search_decoder import BeamSearchDecoder       # noqa: F401
+from .sampling_decoder import SamplingDecoder         # noqa: F401
 from .transformer import TransformerDecoder             # noqa: F401
 from .ctc_decoder import CTCDecoder                       # noqa: F401
 from .sequence_labeler import EmbeddingsLabeler, SequenceLabeler  # noqa: F401

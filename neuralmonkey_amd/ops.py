@@ -530,6 +530,27 @@ def beam_topk_step_wide(logits, b, k, logprob_sum, lengths, finished, penalty, e
         _p(rmax_in), _p(rlse_in), _p(stats), tile or 0), "nm_beam_topk_step_wide")
 
 
+def sample_step(logits, salt_base, salt_step: int, end_id: int, finished, logprob_sum, lengths, out_symbol, out_logprob,
+                out_kept, out_finished, out_logprob_sum, out_lengths, temperature: float = 1.0, top_k: int = 0,
+                top_p: float = 1.0, all_finished=None, workspace=None, inv_temperature: Optional[float] = None):
+    """One truncated sampling step per row of ``logits`` (nm_sample_step, include/nmhip_sample.h): temperature, top-k,
+    then nucleus truncation; the draw is nm_gumbel_argmax's over the kept entries with the salt
+    ``salt_base[0] + salt_step`` (``salt_base``: one int32 / uint32 word on the device, so that a captured graph
+    draws afresh when the word is rewritten); per row the symbol, its log-probability under the truncated
+    distribution, the size of the kept set, and the loop state (finished, summed log-probability, length).  The
+    kernel multiplies by ``inv_temperature`` (default: 1 / temperature rounded to float32)."""
+    lib = _lib.load()
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype == torch.float32
+    assert salt_base.numel() == 1 and salt_base.element_size() == 4
+    inv_t = float(inv_temperature) if inv_temperature is not None else 1.0 / float(temperature)
+    _lib.check(lib.nm_sample_step(
+        _stream(), logits.data_ptr(), logits.stride(0), logits.shape[0], logits.shape[1], inv_t, int(top_k),
+        float(top_p), salt_base.data_ptr(), int(salt_step) & 0xFFFFFFFF, end_id, finished.data_ptr(),
+        logprob_sum.data_ptr(), lengths.data_ptr(), out_symbol.data_ptr(), out_logprob.data_ptr(), out_kept.data_ptr(),
+        out_finished.data_ptr(), out_logprob_sum.data_ptr(), out_lengths.data_ptr(), _p(all_finished), _p(workspace),
+        0 if workspace is None else workspace.numel() * workspace.element_size()), "nm_sample_step")
+
+
 def attn_partials_layout(rows, s, a, c):
     """(nchunk, pctx offset, pstat offset) in floats inside the attention workspace, or None when the shape is
     served by the any-shape kernel (no split-S partials)."""
