@@ -293,6 +293,13 @@ SAMPLE_SIGNATURES = {
     "nm_sample_lds_max_columns": (L, []),
 }
 
+# ... and every symbol include/nmhip_mbr.h declares (minimum Bayes risk decoding over the samples of a sentence: the
+# pairwise utilities and the choice of MBRDecoder, csrc/nm_mbr.hip)
+MBR_SIGNATURES = {
+    "nm_mbr_pairwise": (I, [P, I, P, L, L, L, L, ctypes.c_int32, P]),
+    "nm_mbr_select": (I, [P, P, P, L, L, L, L, P, P, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -368,7 +375,7 @@ def load():
                               + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
                               + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
                               + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())
-                              + list(SAMPLE_SIGNATURES.items())):
+                              + list(SAMPLE_SIGNATURES.items()) + list(MBR_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

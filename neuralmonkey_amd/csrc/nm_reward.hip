@@ -8,41 +8,16 @@
 //                            positions serially -- every lane reads the same LDS words, a broadcast.  One pass serves
 //                            the four orders: the match length of a window pair, capped at 4, extends the equality of
 //                            the (n-1)-grams by one token.  Integer counts, 64-wide shuffles, no atomics; lane 0
-//                            finishes in double and rounds once.
+//                            finishes in double and rounds once.  (The pass and the score live in nm_ngram.h,
+//                            which nm_mbr.hip shares.)
 //   reinforce_weights_kernel one workgroup: the weights, an integer count of the mask and the two scalars.
 #include "nm_common.h"
+#include "nm_ngram.h"
 #include "../../include/nmhip_reward.h"
 
 namespace {
 
-constexpr int REWARD_MAX_TOKENS = 8192;      // T_ref + T_hyp: 32 KiB of LDS (+ 24 bytes of padding)
-constexpr int REWARD_PAD = 3;                // a window of four that starts at the last token stays inside
 constexpr int RW_THREADS = 1024;
-
-__device__ __forceinline__ int reward_wave_min(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ int reward_wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// e[k] (order n = k + 1): the first index >= k of `s` that holds end_id, or T
-__device__ __forceinline__ void reward_ends(const int32_t* s, int T, int end_id, int lane, int e[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) e[k] = T;
-    for (int i = lane; i < T; i += 64)
-        if (s[i] == end_id) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (i >= k) e[k] = min(e[k], i);
-        }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) e[k] = reward_wave_min(e[k]);
-}
 
 __global__ __launch_bounds__(64) void reward_sentence_kernel(
     int kind, const int32_t* __restrict__ ref, long ref_stride, int Tr, const int32_t* __restrict__ hyp,
@@ -60,59 +35,10 @@ __global__ __launch_bounds__(64) void reward_sentence_kernel(
     reward_ends(sr, Tr, end_id, lane, er);
     reward_ends(sh, Th, end_id, lane, eh);
 
-    // A padding token may compare equal to a real one; that never counts: a window of order k + 1 at j counts only
-    // with j + k < e[k] <= T, where all its tokens are real.
-    int matched[4] = {0, 0, 0, 0};
-    for (int i = lane; i < Th; i += 64) {
-        const int h0 = sh[i], h1 = sh[i + 1], h2 = sh[i + 2], h3 = sh[i + 3];
-        int before[4] = {0, 0, 0, 0}, inref[4] = {0, 0, 0, 0};
-        for (int j = 0; j < i; ++j) {
-            const int len = sh[j] != h0 ? 0 : sh[j + 1] != h1 ? 1 : sh[j + 2] != h2 ? 2 : sh[j + 3] != h3 ? 3 : 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) before[k] += (len > k && j + k < eh[k]) ? 1 : 0;
-        }
-        for (int j = 0; j < Tr; ++j) {
-            const int len = sr[j] != h0 ? 0 : sr[j + 1] != h1 ? 1 : sr[j + 2] != h2 ? 2 : sr[j + 3] != h3 ? 3 : 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) inref[k] += (len > k && j + k < er[k]) ? 1 : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) matched[k] += (i + k < eh[k] && before[k] < inref[k]) ? 1 : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) matched[k] = reward_wave_sum(matched[k]);
+    int matched[4];
+    reward_matched(sh, Th, eh, sr, Tr, er, lane, matched);
     if (lane != 0) return;
-
-    int tot_h[4], tot_r[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        tot_h[k] = max(0, eh[k] - k);
-        tot_r[k] = max(0, er[k] - k);
-    }
-    double score = 0.0;
-    if (kind == 0) {
-        if (tot_h[0] > 0) {
-            long long pm = matched[0], pt = tot_h[0];             // at most 8192^4 = 2^52
-#pragma unroll
-            for (int k = 1; k < 4; ++k) {
-                pm *= matched[k] + 1;
-                pt *= tot_h[k] + 1;
-            }
-            const double precision = pow((double)pm / (double)pt, 0.25);
-            const double brevity = fmin(1.0, exp(1.0 - (double)er[0] / (double)tot_h[0]));
-            score = brevity * precision;
-        }
-    } else {
-        int sm = 0, sth = 0, str = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            sm += matched[k];
-            sth += tot_h[k];
-            str += tot_r[k];
-        }
-        if (sth > 0 && str > 0) score = fmin((double)sm / (double)sth, (double)sm / (double)str);
-    }
-    out[b] = (float)score;
+    out[b] = (float)reward_score(kind, matched, eh, er);
 }
 
 __global__ __launch_bounds__(RW_THREADS) void reinforce_weights_kernel(

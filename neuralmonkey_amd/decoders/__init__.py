@@ -7,3 +7,4 @@ from .sequence_labeler import EmbeddingsLabeler, SequenceLabeler  # noqa: F401
 from .classifier import Classifier                       # noqa: F401
 from .sequence_regressor import SequenceRegressor        # noqa: F401
 from .word_alignment_decoder import WordAlignmentDecoder  # noqa: F401
+from .mbr_decoder import MBRDecoder                      # noqa: F401  (last: it imports the utilities of trainers/)

@@ -2369,6 +2369,47 @@ def reinforce_weights(reward, baseline, mask, weight, weights, grad_scale, inv_c
     return weights
 
 
+# ---- minimum Bayes risk decoding over samples (include/nmhip_mbr.h, csrc/nm_mbr.hip) ------------------------------------------
+def _mbr_samples(token_ids):
+    """(row stride, T, B, n) of the samples [T, B, n] int32: sample j of sentence b at ``b * n + j`` of a row."""
+    assert _i32(token_ids).dim() == 3, tuple(token_ids.shape)
+    steps, bsz, n = token_ids.shape
+    assert n == 1 or token_ids.stride(2) == 1, "unit sample stride"
+    assert bsz == 1 or token_ids.stride(1) == n, "the samples of a sentence side by side"
+    return (token_ids.stride(0) if steps > 1 else max(token_ids.stride(0), bsz * n)), steps, bsz, n
+
+
+def mbr_pairwise(kind, token_ids, end_id, out=None):
+    """``out`` [B, n, n] float32: the sentence-level BLEU (``kind`` "bleu") or GLEU ("gleu") of every ordered pair of
+    the ``n`` samples of a sentence, ``out[b, i, j]`` with sample ``j`` as the reference and sample ``i`` as the
+    hypothesis.  ``token_ids`` [T, B, n] int32 as ``SamplingOutput.token_ids`` (any row stride)."""
+    stride, steps, bsz, n = _mbr_samples(token_ids)
+    if out is None:
+        out = torch.empty((bsz, n, n), dtype=torch.float32, device=token_ids.device)
+    assert tuple(_f32(out).shape) == (bsz, n, n) and out.is_contiguous()
+    _lib.check(_lib.load().nm_mbr_pairwise(_stream(), REWARD_KINDS[kind], token_ids.data_ptr(), stride, steps, bsz, n,
+                                           int(end_id), out.data_ptr()), "nm_mbr_pairwise")
+    return out
+
+
+def mbr_select(utilities, token_ids, expected=None, best=None, chosen=None):
+    """(``expected`` [B, n] float32, ``best`` [B] int32, ``chosen`` [T, B] int32) from ``utilities`` [B, n, n] of any
+    origin: the mean of every row (summed in double, in index order), the row with the largest sum (ties to the lowest
+    index, NaN last) and that sample's column of ``token_ids`` [T, B, n]."""
+    stride, steps, bsz, n = _mbr_samples(token_ids)
+    assert tuple(_f32(utilities).shape) == (bsz, n, n) and utilities.is_contiguous()
+    dev = token_ids.device
+    expected = torch.empty((bsz, n), dtype=torch.float32, device=dev) if expected is None else expected
+    best = torch.empty((bsz,), dtype=torch.int32, device=dev) if best is None else best
+    chosen = torch.empty((steps, bsz), dtype=torch.int32, device=dev) if chosen is None else chosen
+    assert tuple(_f32(expected).shape) == (bsz, n) and expected.is_contiguous()
+    assert tuple(_i32(best).shape) == (bsz,) and best.is_contiguous()
+    assert tuple(_i32(chosen).shape) == (steps, bsz) and chosen.is_contiguous()
+    _lib.check(_lib.load().nm_mbr_select(_stream(), utilities.data_ptr(), token_ids.data_ptr(), stride, steps, bsz, n,
+                                         expected.data_ptr(), best.data_ptr(), chosen.data_ptr()), "nm_mbr_select")
+    return expected, best, chosen
+
+
 # ---- REINFORCE with sentence-level feedback (include/nmhip_rl.h, csrc/nm_rl.hip) --------------------------------------------
 def eval_sentence_score_max_tokens() -> int:
     return int(_lib.load().nm_eval_sentence_score_max_tokens())
