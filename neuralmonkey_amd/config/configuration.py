@@ -57,6 +57,10 @@ def load_experiment(path: str, changes: Optional[List[str]] = None, initialize: 
     model = cfg.build_model()
     if getattr(model, "tf_manager", None) is None:
         model.tf_manager = TensorFlowManager(num_sessions=1, num_threads=4, device=device, seed=seed)
+    elif seed is not None and getattr(model.tf_manager, "seed", seed) is None:
+        # a [tf_manager] section has no seed of its own: without this the variables were drawn from the system's
+        # entropy whatever the caller asked for, and every run of a seeded experiment began somewhere else
+        model.tf_manager.reseed(seed)
     trainer = getattr(model, "trainer", None)
     model.trainers = trainer if isinstance(trainer, list) else ([trainer] if trainer is not None else [])
     runners = getattr(model, "runners", None) or []

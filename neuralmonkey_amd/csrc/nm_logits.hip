@@ -84,7 +84,7 @@ __global__ __launch_bounds__(NT) void row_stats_kernel(const float* __restrict__
     if (threadIdx.x == 0) {
         if (max_out) max_out[row] = bv;
         if (lse_out) lse_out[row] = logf(s);
-        if (argmax_out) argmax_out[row] = bi;
+        if (argmax_out) argmax_out[row] = bi < V ? bi : 0;     // no element above -inf (all -inf / NaN): the first index
     }
 }
 
@@ -173,7 +173,8 @@ __global__ __launch_bounds__(NT) void xent_kernel(float* __restrict__ x, long ld
         // -sum_v q_v log p_v with q = (1-eps)*onehot + eps/V  (tf.losses.softmax_cross_entropy label_smoothing)
         const float nll = (t >= 0 && t < V) ? -(xr[t] - bv - lse) : 0.0f;
         const float uniform = (bv + lse) - sx / (float)V;
-        loss_rows[row] = ((1.0f - smoothing) * nll + smoothing * uniform) * w;
+        // (without smoothing `uniform` is not part of the loss: it is +inf beside a -inf class, and 0 * inf is NaN)
+        loss_rows[row] = (smoothing != 0.0f ? (1.0f - smoothing) * nll + smoothing * uniform : nll) * w;
     }
     if (write_grad) {
         __syncthreads();   // loss read of xr[t] done before overwrite
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(1024) void xent_regs_kernel(float* __restrict__ x, 
     if (tid == 0 && loss_rows) {
         const float nll = (t >= 0 && t < V) ? -(x[row * ldx + t] - bv - lse) : 0.0f;    // not yet overwritten: see barrier
         const float uniform = (bv + lse) - sx / (float)V;
-        loss_rows[row] = ((1.0f - smoothing) * nll + smoothing * uniform) * w;
+        loss_rows[row] = (smoothing != 0.0f ? (1.0f - smoothing) * nll + smoothing * uniform : nll) * w;   // see xent_kernel
     }
     if (!write_grad) return;
     __syncthreads();                       // the loss read of x[t] precedes every store of this row
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(XC_NT) void xent_cols_kernel(float* __restrict__ x,
         if (tid == 0 && loss_rows) {
             const float nll = (t >= 0 && t < V) ? -(xt - bv - lse) : 0.0f;
             const float uniform = (bv + lse) - sx / (float)V;
-            loss_rows[row] = ((1.0f - smoothing) * nll + smoothing * uniform) * w;
+            loss_rows[row] = (smoothing != 0.0f ? (1.0f - smoothing) * nll + smoothing * uniform : nll) * w;   // see xent_kernel
         }
         const float gs = w * gsc;
         const float inv = 1.0f / s;
@@ -731,7 +732,7 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(const float* __restrict_
     if (tid == 0) {
         if (max_out) max_out[r] = bv;
         if (lse_out) lse_out[r] = lse;
-        if (argmax_out) argmax_out[r] = bi;
+        if (argmax_out) argmax_out[r] = bi < V ? bi : 0;       // no element above -inf (all -inf / NaN): the first index
     }
     if (!TOPK) return;
     const float lps = logprob_sum[r];

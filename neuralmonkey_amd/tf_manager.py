@@ -55,6 +55,14 @@ class TensorFlowManager:
         self.variables_files: List[str] = []
         self._best_vars_file: Optional[str] = None
 
+    def reseed(self, seed: int) -> None:
+        """Seed the sessions of a manager built without one; before the variables are created."""
+        if any(sess.store.theta is not None for sess in self.sessions):
+            raise RuntimeError("reseed: the variables exist already")
+        self.seed = seed
+        for i, sess in enumerate(self.sessions):
+            sess.seed = sess.store.seed = seed + i
+
     # -- n-best bookkeeping (tf_manager.py:96-155) ---------------------------------
     @property
     def best_vars_file(self) -> str:

@@ -325,6 +325,24 @@ def test_ini_builds_the_plugin_surface(tmp_path):
     assert len(model2.runners) == 2
 
 
+def test_seed_reaches_the_variables_of_a_manager_the_ini_builds(tmp_path):
+    """``load_experiment(seed=...)`` with a [tf_manager] section in the INI (which has no seed of its own): the same
+    seed gives the same initial variables, another seed others; the manager's sessions carry it."""
+    import torch
+    from neuralmonkey_amd.config.configuration import load_experiment
+    path = write_ini(tmp_path)
+    with open(path) as fh:
+        assert "[tf_manager]" in fh.read()
+    thetas = []
+    for seed in (5, 5, 6):
+        model = load_experiment(path, seed=seed)
+        assert model.tf_manager.seed == seed and model.tf_manager.sessions[0].seed == seed
+        thetas.append(model.tf_manager.sessions[0].store.theta.cpu().clone())
+    assert torch.equal(thetas[0], thetas[1]) and not torch.equal(thetas[0], thetas[2])
+    with pytest.raises(RuntimeError, match="exist already"):
+        model.tf_manager.reseed(7)
+
+
 def test_lazy_losses_fill_in_on_first_access():
     """ExecutionResult.losses of a training step: a dict whose values are still on their way to the host."""
     import json
