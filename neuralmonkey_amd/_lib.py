@@ -300,6 +300,13 @@ MBR_SIGNATURES = {
     "nm_mbr_select": (I, [P, P, P, L, L, L, L, P, P, P]),
 }
 
+# ... and every symbol include/nmhip_ctc_beam.h declares (CTC prefix beam search of CTCBeamSearchDecoder,
+# csrc/nm_ctc_beam.hip)
+CTC_BEAM_SIGNATURES = {
+    "nm_ctc_beam_workspace_bytes": (L, [L, L, L, L]),
+    "nm_ctc_beam_search": (I, [P, P, L, L, L, L, L, P, L, I, ctypes.c_int32, P, P, P, P, L]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -375,7 +382,8 @@ def load():
                               + list(ALIGN_SIGNATURES.items()) + list(SPEECH_SIGNATURES.items())
                               + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
                               + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())
-                              + list(SAMPLE_SIGNATURES.items()) + list(MBR_SIGNATURES.items())):
+                              + list(SAMPLE_SIGNATURES.items()) + list(MBR_SIGNATURES.items())
+                              + list(CTC_BEAM_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -227,7 +227,8 @@ class CTCDecoder(ModelPart):
         one all-END row, from which ``vectors_to_sentences`` reads the batch size and empty sentences)."""
         if self.beam_width != 1:
             raise NotImplementedError("CTCDecoder '{}': beam_width = {} needs tf.nn.ctc_beam_search_decoder, which this "
-                                      "engine does not implement (greedy decoding only: beam_width = 1)"
+                                      "engine does not implement (greedy decoding only: beam_width = 1); wrap the "
+                                      "decoder in decoders.ctc_beam_search.CTCBeamSearchDecoder for a beam search"
                                       .format(self.name, self.beam_width))
         logits = self.logits(ctx)
         steps, bsz, _ = logits.shape

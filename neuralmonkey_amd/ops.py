@@ -1762,6 +1762,38 @@ def ctc_greedy(logits, frame_len, merge_repeated, end_token, tokens, out_len, wo
     return tokens, out_len
 
 
+# ---- CTC prefix beam search (include/nmhip_ctc_beam.h, csrc/nm_ctc_beam.hip) ------------------------------------------
+_CTC_BEAM_WS = {}
+
+
+def ctc_beam_workspace_bytes(bsz: int, steps: int, classes: int, beam_size: int) -> int:
+    return int(_lib.load().nm_ctc_beam_workspace_bytes(bsz, steps, classes, beam_size))
+
+
+def ctc_beam_search(logits, frame_len, beam_size, merge_repeated, end_token, tokens, out_len, score, workspace=None):
+    """tf.nn.ctc_beam_search_decoder(top_paths=1) over logits [T, B, K] (blank = K - 1) with ``beam_size`` in 1..64:
+    tokens [B, T] int32 = the classes of each sentence's best prefix, then ``end_token``; out_len [B] int32 = how many;
+    score [B] = the log-probability of that prefix.  The workspace is kept per (device, stream, workspace tag) and
+    grows to the largest call seen."""
+    steps, bsz, k = _ctc_logits(logits)
+    assert tuple(tokens.shape) == (bsz, steps) and (tokens.numel() == 0 or tokens.is_contiguous())
+    assert out_len.numel() == bsz and frame_len.numel() == bsz and score.numel() == bsz and score.is_contiguous()
+    if workspace is None:
+        need = ctc_beam_workspace_bytes(bsz, steps, k, beam_size)
+        if need < 0:
+            _lib.check(-1, "nm_ctc_beam_workspace_bytes")
+        key = (logits.device, _stream(), workspace_tag())
+        workspace = _CTC_BEAM_WS.get(key)
+        if workspace is None or workspace.numel() < need:
+            workspace = _CTC_BEAM_WS[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=logits.device)
+    _lib.check(_lib.load().nm_ctc_beam_search(_stream(), logits.data_ptr(), logits.stride(0), logits.stride(1), steps, bsz,
+                                              k, _i32(frame_len).data_ptr(), int(beam_size), int(bool(merge_repeated)),
+                                              int(end_token), _i32(tokens).data_ptr(), _i32(out_len).data_ptr(),
+                                              _f32(score).data_ptr(), workspace.data_ptr(), workspace.numel()),
+               "nm_ctc_beam_search")
+    return tokens, out_len, score
+
+
 # ---- sequence labelling (include/nmhip_label.h, csrc/nm_label.hip) ----------------------------------------------------
 def label_rows_max_classes() -> int:
     return int(_lib.load().nm_label_rows_max_classes())
