@@ -307,6 +307,14 @@ CTC_BEAM_SIGNATURES = {
     "nm_ctc_beam_search": (I, [P, P, L, L, L, L, L, P, L, I, ctypes.c_int32, P, P, P, P, L]),
 }
 
+# ... and every symbol include/nmhip_edit.h declares (the edit-distance scores of sentences: the reward of
+# SelfCriticalObjective and the utility of MBRDecoder for speech and character-level models, csrc/nm_edit.hip)
+EDIT_SIGNATURES = {
+    "nm_edit_max_tokens": (L, []),
+    "nm_edit_reward": (I, [P, I, P, L, L, P, L, L, L, ctypes.c_int32, P, P]),
+    "nm_edit_pairwise": (I, [P, I, P, L, L, L, L, ctypes.c_int32, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -383,7 +391,7 @@ def load():
                               + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
                               + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())
                               + list(SAMPLE_SIGNATURES.items()) + list(MBR_SIGNATURES.items())
-                              + list(CTC_BEAM_SIGNATURES.items())):
+                              + list(CTC_BEAM_SIGNATURES.items()) + list(EDIT_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -8,7 +8,9 @@ The reference has no such decoder.  Candidates and evidence are the same samples
     best[b]        = argmax_i expected[b, i]              (on the double sums; ties to the lowest i, NaN last)
 
 ``sentence_gleu`` (the default) and ``sentence_bleu`` of trainers/self_critical_objective.py are recognised by identity
-and scored on the device, one wavefront per unordered pair (nm_mbr_pairwise, csrc/nm_mbr.hip).  Any other callable gets
+and scored on the device, one wavefront per unordered pair (nm_mbr_pairwise, csrc/nm_mbr.hip); so are
+``sentence_edit_accuracy`` and ``sentence_neg_wer``, the utilities of speech and character-level models, up to
+``ops.edit_max_tokens()`` steps (nm_edit_pairwise, csrc/nm_edit.hip).  Any other callable gets
 the convention of ``SelfCriticalObjective.reward_function``: it is called ONCE on the host with the ``B * n * n`` pairs
 tiled side by side, time-major, and its result travels back.  Either way the sums, the choice and the gather of the
 chosen column are one launch (nm_mbr_select): no torch kernel runs on this path.
@@ -21,7 +23,7 @@ import torch
 from .. import ops
 from ..model.model_part import ModelPart
 from ..runtime import tensor
-from ..trainers.self_critical_objective import DEVICE_REWARDS, sentence_gleu
+from ..trainers.self_critical_objective import DEVICE_EDIT_REWARDS, DEVICE_REWARDS, sentence_gleu
 from ..vocabulary import END_TOKEN_INDEX, Vocabulary
 from .sampling_decoder import SamplingDecoder, SamplingOutput
 
@@ -75,9 +77,11 @@ class MBRDecoder(ModelPart):
                              torch.zeros((bsz, n, n)), samples)
         key = (id(self), "mbr", bsz, n)
         utilities = ctx.buffer(key + ("U",), (bsz, n, n))
-        kind = DEVICE_REWARDS.get(self.utility)
+        kind, edit_kind = DEVICE_REWARDS.get(self.utility), DEVICE_EDIT_REWARDS.get(self.utility)
         if kind is not None and tok.is_cuda:
             ops.mbr_pairwise(kind, tok, END_TOKEN_INDEX, out=utilities)
+        elif edit_kind is not None and tok.is_cuda and steps <= ops.edit_max_tokens():
+            ops.edit_pairwise(edit_kind, tok, END_TOKEN_INDEX, out=utilities)
         else:
             references, hypotheses = tile_pairs(tok.cpu().numpy())
             host = self.utility(references, hypotheses.astype(np.int64))

@@ -2442,6 +2442,52 @@ def mbr_select(utilities, token_ids, expected=None, best=None, chosen=None):
     return expected, best, chosen
 
 
+# ---- edit-distance scores of sentences (include/nmhip_edit.h, csrc/nm_edit.hip) ---------------------------------------------------
+EDIT_KINDS = {"accuracy": 0, "neg_wer": 1}
+
+
+def edit_max_tokens() -> int:
+    """The longest token column ``edit_reward`` and ``edit_pairwise`` take."""
+    return int(_lib.load().nm_edit_max_tokens())
+
+
+def edit_reward(kind, references, hypotheses, end_id, out=None, dist=None):
+    """The edit accuracy ``1 - d / max(lr, lh)`` (``kind`` "accuracy") or the negative word error rate
+    ``-d / max(lr, 1)`` ("neg_wer") of every sentence, ``d`` the Levenshtein distance of the two columns cut at their
+    first ``end_id``: ``references`` [T_ref, B] and ``hypotheses`` [T_hyp, B] are int32, time-major, with unit batch
+    stride and any row stride.  ``dist`` [B] int32, if given, receives the distances."""
+    lib = _lib.load()
+    _i32(references), _i32(hypotheses)
+    assert references.dim() == 2 and hypotheses.dim() == 2 and references.shape[1] == hypotheses.shape[1]
+    bsz = references.shape[1]
+    strides = []
+    for t in (references, hypotheses):
+        assert bsz == 1 or t.stride(1) == 1, "unit batch stride"
+        strides.append(t.stride(0) if t.shape[0] > 1 else max(t.stride(0), bsz))
+    if out is None:
+        out = torch.empty(bsz, dtype=torch.float32, device=references.device)
+    assert _f32(out).numel() == bsz and out.is_contiguous()
+    assert dist is None or (_i32(dist).numel() == bsz and dist.is_contiguous())
+    _lib.check(lib.nm_edit_reward(_stream(), EDIT_KINDS[kind], references.data_ptr(), strides[0], references.shape[0],
+                                  hypotheses.data_ptr(), strides[1], hypotheses.shape[0], bsz, int(end_id),
+                                  out.data_ptr(), _p(dist)), "nm_edit_reward")
+    return out
+
+
+def edit_pairwise(kind, token_ids, end_id, out=None):
+    """``out`` [B, n, n] float32: the edit accuracy (``kind`` "accuracy") or negative word error rate ("neg_wer") of
+    every ordered pair of the ``n`` samples of a sentence, in the layout of ``mbr_pairwise``: ``out[b, i, j]`` has
+    sample ``j`` as the reference and sample ``i`` as the hypothesis.  ``token_ids`` [T, B, n] int32 as
+    ``SamplingOutput.token_ids`` (any row stride); ``mbr_select`` takes the result."""
+    stride, steps, bsz, n = _mbr_samples(token_ids)
+    if out is None:
+        out = torch.empty((bsz, n, n), dtype=torch.float32, device=token_ids.device)
+    assert tuple(_f32(out).shape) == (bsz, n, n) and out.is_contiguous()
+    _lib.check(_lib.load().nm_edit_pairwise(_stream(), EDIT_KINDS[kind], token_ids.data_ptr(), stride, steps, bsz, n,
+                                            int(end_id), out.data_ptr()), "nm_edit_pairwise")
+    return out
+
+
 # ---- REINFORCE with sentence-level feedback (include/nmhip_rl.h, csrc/nm_rl.hip) --------------------------------------------
 def eval_sentence_score_max_tokens() -> int:
     return int(_lib.load().nm_eval_sentence_score_max_tokens())

@@ -11,8 +11,10 @@ MI355X mapping: the reference computes the rewards in Python behind ``tf.py_func
 four ``Counter`` loops per sentence and per decoding.  Here ``sentence_bleu`` and ``sentence_gleu`` are recognised by
 identity and run as ONE small kernel each (csrc/nm_reward.hip: a wavefront per sentence); ``nm_reinforce_weights`` turns
 rewards and mask into the row weights and the device scalars of ``nm_xent`` over the taped runtime logits, whose
-gradient is written in place.  After the decoding loop the step reads nothing back.  Any other callable gets the
-reference's treatment: both arrays travel to the host and the result travels back.
+gradient is written in place.  After the decoding loop the step reads nothing back.  ``sentence_edit_accuracy`` and
+``sentence_neg_wer`` (minimum-WER training; the rule is this project's) are recognised the same way and run
+as one launch of csrc/nm_edit.hip.  Any other callable gets the reference's treatment: both arrays travel to the host
+and the result travels back.
 """
 from typing import Callable, NamedTuple
 
@@ -103,8 +105,48 @@ def sentence_gleu(references: np.ndarray, hypotheses: np.ndarray) -> np.ndarray:
     return np.array(scores, dtype=np.float32)
 
 
+def _edit_counts(ref: np.ndarray, hyp: np.ndarray):
+    """(d, lr, lh): the Levenshtein distance of the two sentences ``seq[:e_1]`` and their lengths -- integers.
+
+    Row ``i`` of the table from row ``i - 1``: ``open[j] = min(up + 1, diagonal + (tokens differ))`` for all ``j`` at
+    once; the chain through the left neighbour, ``row[j] = min(open[j], row[j - 1] + 1)``, is a running minimum of
+    ``open[j] - j``."""
+    lr, lh = _ngram_ends(ref)[0], _ngram_ends(hyp)[0]
+    hyp, columns = np.asarray(hyp[:lh]), np.arange(lh + 1)
+    row = columns.copy()
+    for i in range(lr):
+        opened = np.concatenate(([i + 1], np.minimum(row[1:] + 1, row[:-1] + (hyp != ref[i]))))
+        row = np.minimum.accumulate(opened - columns) + columns
+    return int(row[lh]), lr, lh
+
+
+def sentence_edit_accuracy(references: np.ndarray, hypotheses: np.ndarray) -> np.ndarray:
+    """``1 - d / max(lr, lh)`` of time-major ``references`` [T_ref, B] and ``hypotheses`` [T_hyp, B], ``d`` the
+    Levenshtein distance over token indices of the two sentences, each cut at its first end token (whatever else the
+    decoder emitted is a token), ``lr`` and ``lh`` their lengths; 1 when both are empty.  Symmetric, in [0, 1]: the
+    character or word accuracy of speech recognition as a sentence-level utility."""
+    scores = []
+    for ref, hyp in zip(np.transpose(references), np.transpose(hypotheses)):
+        dist, n_ref, n_hyp = _edit_counts(ref, hyp)
+        longer = max(n_ref, n_hyp)
+        scores.append(1.0 if longer == 0 else 1.0 - np.float64(dist) / np.float64(longer))
+    return np.array(scores, dtype=np.float32)
+
+
+def sentence_neg_wer(references: np.ndarray, hypotheses: np.ndarray) -> np.ndarray:
+    """``-d / max(lr, 1)``: the negative word error rate of every sentence, the reward of minimum-WER training."""
+    scores = []
+    for ref, hyp in zip(np.transpose(references), np.transpose(hypotheses)):
+        dist, n_ref, _ = _edit_counts(ref, hyp)
+        scores.append(np.float64(-dist) / np.float64(max(n_ref, 1)))
+    return np.array(scores, dtype=np.float32)
+
+
 # the reward functions that run on the device: function -> ops.sentence_reward kind
 DEVICE_REWARDS = {sentence_bleu: "bleu", sentence_gleu: "gleu"}
+# ... and those of csrc/nm_edit.hip: function -> ops.edit_reward / ops.edit_pairwise kind, for columns of at most
+# ops.edit_max_tokens() positions
+DEVICE_EDIT_REWARDS = {sentence_edit_accuracy: "accuracy", sentence_neg_wer: "neg_wer"}
 
 
 class _Taped(NamedTuple):
@@ -124,13 +166,18 @@ class SelfCriticalObjective(Objective):
 
     # -- rewards ------------------------------------------------------------------------------------------------
     def rewards(self, ctx, references: torch.Tensor, hypotheses: torch.Tensor, tag: str) -> torch.Tensor:
-        """[B] float32 on the device.  The two functions of this module: one kernel launch.  Anything else: the
-        reference's ``tf.py_func`` -- both arrays to the host (a synchronisation), the result back."""
+        """[B] float32 on the device.  The four functions of this module: one kernel launch (the two edit-distance
+        ones up to ``ops.edit_max_tokens()`` positions).  Anything else: the reference's ``tf.py_func`` -- both arrays
+        to the host (a synchronisation), the result back."""
         bsz = references.shape[1]
         out = ctx.buffer((id(self), "reward", tag, bsz), (bsz,))
         kind = DEVICE_REWARDS.get(self.reward_function)
         if kind is not None and references.is_cuda:
             return ops.sentence_reward(kind, references, hypotheses, END_TOKEN_INDEX, out=out)
+        kind = DEVICE_EDIT_REWARDS.get(self.reward_function)
+        if (kind is not None and references.is_cuda
+                and max(references.shape[0], hypotheses.shape[0]) <= ops.edit_max_tokens()):
+            return ops.edit_reward(kind, references, hypotheses, END_TOKEN_INDEX, out=out)
         host = self.reward_function(references.cpu().numpy(), hypotheses.cpu().numpy().astype(np.int64))
         host = np.ascontiguousarray(np.asarray(host, dtype=np.float32).reshape(bsz))
         return out.copy_(torch.from_numpy(host))
