@@ -315,6 +315,14 @@ EDIT_SIGNATURES = {
     "nm_edit_pairwise": (I, [P, I, P, L, L, L, L, ctypes.c_int32, P]),
 }
 
+# ... and every symbol include/nmhip_chrf.h declares (chrF from a character table of the vocabulary: the reward of
+# SelfCriticalObjective and the utility of MBRDecoder given a SentenceChrF, csrc/nm_chrf.hip)
+CHRF_SIGNATURES = {
+    "nm_chrf_max_chars": (L, []),
+    "nm_chrf_reward": (I, [P, P, L, L, P, L, L, L, ctypes.c_int32, P, P, L, L, I, ctypes.c_double, P, P]),
+    "nm_chrf_pairwise": (I, [P, P, L, L, L, L, ctypes.c_int32, P, P, L, L, I, ctypes.c_double, P]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -391,7 +399,8 @@ def load():
                               + list(IMGREAD_SIGNATURES.items()) + list(VGG_SIGNATURES.items())
                               + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())
                               + list(SAMPLE_SIGNATURES.items()) + list(MBR_SIGNATURES.items())
-                              + list(CTC_BEAM_SIGNATURES.items()) + list(EDIT_SIGNATURES.items())):
+                              + list(CTC_BEAM_SIGNATURES.items()) + list(EDIT_SIGNATURES.items())
+                              + list(CHRF_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -10,7 +10,9 @@ The reference has no such decoder.  Candidates and evidence are the same samples
 ``sentence_gleu`` (the default) and ``sentence_bleu`` of trainers/self_critical_objective.py are recognised by identity
 and scored on the device, one wavefront per unordered pair (nm_mbr_pairwise, csrc/nm_mbr.hip); so are
 ``sentence_edit_accuracy`` and ``sentence_neg_wer``, the utilities of speech and character-level models, up to
-``ops.edit_max_tokens()`` steps (nm_edit_pairwise, csrc/nm_edit.hip).  Any other callable gets
+``ops.edit_max_tokens()`` steps (nm_edit_pairwise, csrc/nm_edit.hip), and a ``SentenceChrF`` object, chrF
+over the characters of the samples' words, while its static bound fits ``ops.chrf_max_chars()`` (nm_chrf_pairwise,
+csrc/nm_chrf.hip).  Any other callable gets
 the convention of ``SelfCriticalObjective.reward_function``: it is called ONCE on the host with the ``B * n * n`` pairs
 tiled side by side, time-major, and its result travels back.  Either way the sums, the choice and the gather of the
 chosen column are one launch (nm_mbr_select): no torch kernel runs on this path.
@@ -23,7 +25,7 @@ import torch
 from .. import ops
 from ..model.model_part import ModelPart
 from ..runtime import tensor
-from ..trainers.self_critical_objective import DEVICE_EDIT_REWARDS, DEVICE_REWARDS, sentence_gleu
+from ..trainers.self_critical_objective import DEVICE_EDIT_REWARDS, DEVICE_REWARDS, SentenceChrF, sentence_gleu
 from ..vocabulary import END_TOKEN_INDEX, Vocabulary
 from .sampling_decoder import SamplingDecoder, SamplingOutput
 
@@ -82,6 +84,9 @@ class MBRDecoder(ModelPart):
             ops.mbr_pairwise(kind, tok, END_TOKEN_INDEX, out=utilities)
         elif edit_kind is not None and tok.is_cuda and steps <= ops.edit_max_tokens():
             ops.edit_pairwise(edit_kind, tok, END_TOKEN_INDEX, out=utilities)
+        elif isinstance(self.utility, SentenceChrF) and tok.is_cuda and self.utility.on_device(2 * steps):
+            ops.chrf_pairwise(tok, END_TOKEN_INDEX, self.utility.device_table(tok.device), self.utility.n,
+                              self.utility.beta, out=utilities)
         else:
             references, hypotheses = tile_pairs(tok.cpu().numpy())
             host = self.utility(references, hypotheses.astype(np.int64))

@@ -7,7 +7,7 @@ import ctypes
 import struct
 import os
 import threading
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -2485,6 +2485,63 @@ def edit_pairwise(kind, token_ids, end_id, out=None):
     assert tuple(_f32(out).shape) == (bsz, n, n) and out.is_contiguous()
     _lib.check(_lib.load().nm_edit_pairwise(_stream(), EDIT_KINDS[kind], token_ids.data_ptr(), stride, steps, bsz, n,
                                             int(end_id), out.data_ptr()), "nm_edit_pairwise")
+    return out
+
+
+# ---- chrF of sentences from a character table (include/nmhip_chrf.h, csrc/nm_chrf.hip) -----------------------------------------
+class CharTable(NamedTuple):
+    """``SentenceChrF.device_table``: the characters of a vocabulary's words on the device."""
+    rows: torch.Tensor              # [V, 4] int32: (offset, stem_len, whole_len, flags)
+    chars: torch.Tensor             # [total] int16: the bits of the uint16 character ids
+    max_word_chars: int             # the longest whole_len, at least 1
+
+
+def chrf_max_chars() -> int:
+    """The most characters ``chrf_reward`` and ``chrf_pairwise`` stage, by their static bound: the tokens of both
+    columns times ``max_word_chars + 1``."""
+    return int(_lib.load().nm_chrf_max_chars())
+
+
+def _chrf_table(table):
+    assert _i32(table.rows).dim() == 2 and table.rows.shape[1] == 4 and table.rows.is_contiguous()
+    assert table.chars.dtype == torch.int16 and table.chars.is_cuda and table.chars.is_contiguous()
+    return table.rows.data_ptr(), table.chars.data_ptr(), table.rows.shape[0], int(table.max_word_chars)
+
+
+def chrf_reward(references, hypotheses, end_id, table, n=6, beta=1.0, out=None, counts=None):
+    """chrF of order ``n`` of every sentence (the rule of ``SentenceChrF``): ``references`` [T_ref, B] and
+    ``hypotheses`` [T_hyp, B] are int32, time-major, with unit batch stride and any row stride; ``table`` a
+    ``CharTable``.  ``counts`` [B, 3, 6] int32, if given, receives matched, total_h and total_r by order."""
+    lib = _lib.load()
+    _i32(references), _i32(hypotheses)
+    assert references.dim() == 2 and hypotheses.dim() == 2 and references.shape[1] == hypotheses.shape[1]
+    bsz = references.shape[1]
+    strides = []
+    for t in (references, hypotheses):
+        assert bsz == 1 or t.stride(1) == 1, "unit batch stride"
+        strides.append(t.stride(0) if t.shape[0] > 1 else max(t.stride(0), bsz))
+    if out is None:
+        out = torch.empty(bsz, dtype=torch.float32, device=references.device)
+    assert _f32(out).numel() == bsz and out.is_contiguous()
+    assert counts is None or (tuple(_i32(counts).shape) == (bsz, 3, 6) and counts.is_contiguous())
+    _lib.check(lib.nm_chrf_reward(_stream(), references.data_ptr(), strides[0], references.shape[0],
+                                  hypotheses.data_ptr(), strides[1], hypotheses.shape[0], bsz, int(end_id),
+                                  *_chrf_table(table), int(n), float(beta), out.data_ptr(), _p(counts)),
+               "nm_chrf_reward")
+    return out
+
+
+def chrf_pairwise(token_ids, end_id, table, n=6, beta=1.0, out=None):
+    """``out`` [B, n_samples, n_samples] float32: chrF of every ordered pair of the samples of a sentence, in the
+    layout of ``mbr_pairwise``: ``out[b, i, j]`` has sample ``j`` as the reference and sample ``i`` as the
+    hypothesis.  ``token_ids`` [T, B, n_samples] int32 as ``SamplingOutput.token_ids`` (any row stride)."""
+    stride, steps, bsz, samples = _mbr_samples(token_ids)
+    if out is None:
+        out = torch.empty((bsz, samples, samples), dtype=torch.float32, device=token_ids.device)
+    assert tuple(_f32(out).shape) == (bsz, samples, samples) and out.is_contiguous()
+    _lib.check(_lib.load().nm_chrf_pairwise(_stream(), token_ids.data_ptr(), stride, steps, bsz, samples, int(end_id),
+                                            *_chrf_table(table), int(n), float(beta), out.data_ptr()),
+               "nm_chrf_pairwise")
     return out
 
 

@@ -13,10 +13,11 @@ identity and run as ONE small kernel each (csrc/nm_reward.hip: a wavefront per s
 rewards and mask into the row weights and the device scalars of ``nm_xent`` over the taped runtime logits, whose
 gradient is written in place.  After the decoding loop the step reads nothing back.  ``sentence_edit_accuracy`` and
 ``sentence_neg_wer`` (minimum-WER training; the rule is this project's) are recognised the same way and run
-as one launch of csrc/nm_edit.hip.  Any other callable gets the reference's treatment: both arrays travel to the host
-and the result travels back.
+as one launch of csrc/nm_edit.hip; a ``SentenceChrF`` object (the reference's chrF over the characters of the tokens'
+words) as one launch of csrc/nm_chrf.hip.  Any other callable gets the reference's treatment: both arrays
+travel to the host and the result travels back.
 """
-from typing import Callable, NamedTuple
+from typing import Callable, Dict, List, NamedTuple
 
 import numpy as np
 import torch
@@ -26,7 +27,7 @@ from .. import ops
 from ..checking import check_argument_types
 from ..decoders.decoder import Decoder
 from ..runtime import tensor
-from ..vocabulary import END_TOKEN_INDEX
+from ..vocabulary import END_TOKEN_INDEX, Vocabulary
 from .objective import Objective
 
 # pylint: disable=invalid-name
@@ -148,6 +149,131 @@ DEVICE_REWARDS = {sentence_bleu: "bleu", sentence_gleu: "gleu"}
 # ops.edit_max_tokens() positions
 DEVICE_EDIT_REWARDS = {sentence_edit_accuracy: "accuracy", sentence_neg_wer: "neg_wer"}
 
+CHRF_GLUE, CHRF_SPACE_DROPPED = 1, 2                     # the flags of a character-table row (include/nmhip_chrf.h)
+CHRF_SPACE_ID, CHRF_MAX_ORDER, CHRF_MAX_CHARACTERS = 0, 6, 65534
+
+
+def _char_ngrams(chars: List[str], n: int) -> List[Dict[str, int]]:
+    """evaluators/chrf.py:89-97: per order m = 1..n the counts of the m-grams of ``chars``, keyed by their text."""
+    orders = []
+    for m in range(1, n + 1):
+        counted = {}  # type: Dict[str, int]
+        for i in range(len(chars) - m + 1):
+            gram = "".join(chars[i:i + m])
+            counted[gram] = counted.get(gram, 0) + 1
+        orders.append(counted)
+    return orders
+
+
+class SentenceChrF:
+    """chrF (http://www.statmt.org/wmt15/pdf/WMT49.pdf) of time-major index arrays, the reference's
+    ``ChrFEvaluator.score_instance`` (evaluators/chrf.py:35-97) per sentence: a ``reward_function`` of
+    ``SelfCriticalObjective`` and a ``utility`` of ``MBRDecoder``, which recognise the class and score on the device
+    from ``device_table`` (csrc/nm_chrf.hip).  ``n``, ``beta`` and ``ignored_symbols`` default as the
+    reference's do; ``beta=3`` is its ``ChrF3``.  Orders above 6 are not offered.
+
+    The sentence of a column is its tokens before the first ``</s>`` index or index outside the vocabulary; its text is
+    their words joined by spaces -- with ``join_subwords`` after the reference's BPE join, ``.replace("@@ ", "")`` --;
+    its characters are the text's code points without ``ignored_symbols``.  Calling the object is the host statement
+    of the rule, and the route of CPU tensors."""
+
+    def __init__(self, vocabulary: Vocabulary, n: int = 6, beta: float = 1.0, ignored_symbols: List[str] = None,
+                 join_subwords: bool = False) -> None:
+        check_argument_types()
+        if not 1 <= n <= CHRF_MAX_ORDER:
+            raise ValueError("SentenceChrF: n = {} outside 1..{}".format(n, CHRF_MAX_ORDER))
+        if not beta > 0:
+            raise ValueError("SentenceChrF: beta = {} is not above 0".format(beta))
+        self.vocabulary = vocabulary
+        self.n = n
+        self.beta = float(beta)
+        self.ignored = frozenset(ignored_symbols or ())
+        self.join_subwords = join_subwords
+        self.table()                                     # ValueError for a vocabulary the table cannot hold
+
+    # -- the rule, on the host ----------------------------------------------------------------------------------
+    def characters(self, column) -> List[str]:
+        words = self.vocabulary.index_to_word
+        kept = []
+        for index in column:
+            if index == END_TOKEN_INDEX or not 0 <= index < len(words):
+                break
+            kept.append(words[index])
+        text = " ".join(kept)
+        if self.join_subwords:
+            text = text.replace("@@ ", "")
+        return [c for c in text if c not in self.ignored]
+
+    def counts(self, ref_chars: List[str], hyp_chars: List[str]):
+        """(matched, total_h, total_r), each a list over the orders 1..n -- integers."""
+        ref_grams, hyp_grams = _char_ngrams(ref_chars, self.n), _char_ngrams(hyp_chars, self.n)
+        matched = [sum(min(count, ref[gram]) for gram, count in hyp.items() if gram in ref)
+                   for ref, hyp in zip(ref_grams, hyp_grams)]
+        return (matched, [max(0, len(hyp_chars) - m) for m in range(self.n)],
+                [max(0, len(ref_chars) - m) for m in range(self.n)])
+
+    def score(self, ref_chars: List[str], hyp_chars: List[str]) -> float:
+        if not ref_chars or not hyp_chars:
+            return 1.0 if not ref_chars and not hyp_chars else 0.0
+        matched, total_h, total_r = self.counts(ref_chars, hyp_chars)
+        precision = recall = 0.0
+        for hit, n_hyp, n_ref in zip(matched, total_h, total_r):
+            precision += hit / n_hyp if n_hyp else 1.0
+            recall += hit / n_ref if n_ref else 1.0
+        precision /= self.n
+        recall /= self.n
+        if precision == 0.0 and recall == 0.0:
+            return 0.0
+        beta_2 = self.beta * self.beta
+        return (1.0 + beta_2) * (precision * recall) / (beta_2 * precision + recall)
+
+    def __call__(self, references: np.ndarray, hypotheses: np.ndarray) -> np.ndarray:
+        scores = [self.score(self.characters(ref), self.characters(hyp))
+                  for ref, hyp in zip(np.transpose(references), np.transpose(hypotheses))]
+        return np.array(scores, dtype=np.float32)
+
+    # -- the character table ------------------------------------------------------------------------------------
+    def table(self):
+        """(rows int32 [V, 4], chars uint16 [total], max_word_chars) of include/nmhip_chrf.h: per word (offset,
+        stem_len, whole_len, flags) into the dense ids of its kept characters, the stem -- the text without a trailing
+        "@@" -- first; id 0 is the space.  Computed once per (vocabulary, ignored symbols, join) and kept on the
+        vocabulary, with its device copies."""
+        cache = self.vocabulary.__dict__.setdefault("_chrf_tables", {})
+        key = (tuple(sorted(self.ignored)), self.join_subwords)
+        if key not in cache or cache[key][0] != len(self.vocabulary):
+            words = list(self.vocabulary.index_to_word)
+            if not all(w and " " not in w for w in words):
+                raise ValueError("SentenceChrF: the vocabulary has an empty word or a word with a space")
+            ids = {" ": CHRF_SPACE_ID}
+            rows, chars = np.zeros((len(words), 4), np.int32), []
+            dropped = CHRF_SPACE_DROPPED if " " in self.ignored else 0
+            for row, word in zip(rows, words):
+                glue = self.join_subwords and word.endswith("@@")
+                stem = [c for c in (word[:-2] if glue else word) if c not in self.ignored]
+                tail = [c for c in "@@" if c not in self.ignored] if glue else []
+                row[:] = (len(chars), len(stem), len(stem) + len(tail), (CHRF_GLUE if glue else 0) | dropped)
+                chars.extend(ids.setdefault(c, len(ids)) for c in stem + tail)
+            if len(ids) > CHRF_MAX_CHARACTERS:
+                raise ValueError("SentenceChrF: {} distinct characters, the space included, are more than {}"
+                                 .format(len(ids), CHRF_MAX_CHARACTERS))
+            cache[key] = (len(words), rows, np.array(chars or [CHRF_SPACE_ID], np.uint16),
+                          max(1, int(rows[:, 2].max())), {})
+        return cache[key][1:4]
+
+    def device_table(self, device) -> ops.CharTable:
+        """``table`` on ``device``, copied there once per device."""
+        rows, chars, max_word_chars = self.table()
+        on_devices = self.vocabulary.__dict__["_chrf_tables"][(tuple(sorted(self.ignored)), self.join_subwords)][4]
+        name = str(torch.device(device))
+        if name not in on_devices:
+            on_devices[name] = ops.CharTable(torch.from_numpy(rows).to(device),
+                                             torch.from_numpy(chars.view(np.int16)).to(device), max_word_chars)
+        return on_devices[name]
+
+    def on_device(self, tokens: int) -> bool:
+        """Whether columns of ``tokens`` positions together fit the kernels' static bound."""
+        return tokens * (self.table()[2] + 1) <= ops.chrf_max_chars()
+
 
 class _Taped(NamedTuple):
     """What ``Decoder._general_backward`` reads of a train result."""
@@ -167,8 +293,9 @@ class SelfCriticalObjective(Objective):
     # -- rewards ------------------------------------------------------------------------------------------------
     def rewards(self, ctx, references: torch.Tensor, hypotheses: torch.Tensor, tag: str) -> torch.Tensor:
         """[B] float32 on the device.  The four functions of this module: one kernel launch (the two edit-distance
-        ones up to ``ops.edit_max_tokens()`` positions).  Anything else: the reference's ``tf.py_func`` -- both arrays
-        to the host (a synchronisation), the result back."""
+        ones up to ``ops.edit_max_tokens()`` positions); so is a ``SentenceChrF`` while its static bound fits
+        ``ops.chrf_max_chars()``.  Anything else: the reference's ``tf.py_func`` -- both arrays to the host (a
+        synchronisation), the result back."""
         bsz = references.shape[1]
         out = ctx.buffer((id(self), "reward", tag, bsz), (bsz,))
         kind = DEVICE_REWARDS.get(self.reward_function)
@@ -178,6 +305,11 @@ class SelfCriticalObjective(Objective):
         if (kind is not None and references.is_cuda
                 and max(references.shape[0], hypotheses.shape[0]) <= ops.edit_max_tokens()):
             return ops.edit_reward(kind, references, hypotheses, END_TOKEN_INDEX, out=out)
+        chrf = self.reward_function
+        if (isinstance(chrf, SentenceChrF) and references.is_cuda
+                and chrf.on_device(references.shape[0] + hypotheses.shape[0])):
+            return ops.chrf_reward(references, hypotheses, END_TOKEN_INDEX, chrf.device_table(references.device),
+                                   chrf.n, chrf.beta, out=out)
         host = self.reward_function(references.cpu().numpy(), hypotheses.cpu().numpy().astype(np.int64))
         host = np.ascontiguousarray(np.asarray(host, dtype=np.float32).reshape(bsz))
         return out.copy_(torch.from_numpy(host))
