@@ -323,6 +323,16 @@ CHRF_SIGNATURES = {
     "nm_chrf_pairwise": (I, [P, P, L, L, L, L, ctypes.c_int32, P, P, L, L, I, ctypes.c_double, P]),
 }
 
+# ... and every symbol include/nmhip_sdp_stream.h declares (scaled dot-product attention over sequences past the LDS bound
+# of nm_sdp_attn_fwd / nm_sdp_attn_bwd: streamed key / value tiles, online softmax, csrc/nm_sdp_stream.hip)
+SDP_STREAM_SIGNATURES = {
+    "nm_sdp_stream_wanted": (I, [L, L, L, I]),
+    "nm_sdp_stream_workspace_bytes": (L, [L, L, L]),
+    "nm_sdp_stream_fwd": (I, [P, P, L, P, L, P, L, P, L, L, L, L, L, L, L, I, F, ctypes.c_uint32, P, P, L, P, P, P]),
+    "nm_sdp_stream_bwd": (I, [P, P, L, P, L, P, L, P, L, P, L, P, P, P, L, L, L, L, L, L, L, I, F, ctypes.c_uint32, P,
+                              P, L, P, L, P, L, P, I]),
+}
+
 
 class NMHipError(RuntimeError):
     pass
@@ -400,7 +410,7 @@ def load():
                               + list(SPLIT_SIGNATURES.items()) + list(BEAM_WIDE_SIGNATURES.items())
                               + list(SAMPLE_SIGNATURES.items()) + list(MBR_SIGNATURES.items())
                               + list(CTC_BEAM_SIGNATURES.items()) + list(EDIT_SIGNATURES.items())
-                              + list(CHRF_SIGNATURES.items())):
+                              + list(CHRF_SIGNATURES.items()) + list(SDP_STREAM_SIGNATURES.items())):
         fn = getattr(lib, name)       # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

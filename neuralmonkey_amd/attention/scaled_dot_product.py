@@ -10,6 +10,8 @@ and value projections do not depend on the decoder step and are computed once pe
 (the reference re-computes them inside the while-loop body), query / output projections per step.
 The fused kernel ``nm_sdp_attn_fwd`` scores, masks (``e*m + (1-m)*-1e9``, :45-69), soft-maxes,
 drops out and sums a head's keys from LDS; k hypotheses of a sentence share its keys (row // k).
+Sources longer than its LDS bound (301 positions at head width 64, 153 at 128) go to ``nm_sdp_stream_fwd``, which
+streams the keys and values in tiles -- or, for one query per row, to the one-query kernel, which has no bound.
 
 Constraints the reference imposes through tensor shapes (:151-166) are checked up front: the key
 dimension equals the query (decoder state) size, and so does the value dimension when there are

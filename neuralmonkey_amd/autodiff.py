@@ -816,10 +816,15 @@ def sdp_attention(tape: Tape, q: Var, k: Var, v: Var, key_mask: Optional[torch.T
     the (post-dropout) weights, e.g. a decoder's attention history."""
     d = q.shape[1]
     out = tape.new((bq * tq, d))
-    w = w_out if w_out is not None else (tape.buf((bq, heads, tq, tk)) if tape.recording else None)
     k3 = k_data if k_data is not None else k.data.view(bk, tk, d)
     v3 = v_data if v_data is not None else v.data.view(bk, tk, d)
     step = tape.ctx.session.step_tensor() if keep_prob < 1.0 else None
+    # decided once, here: past the LDS bound of the resident kernels the keys and values stream through LDS in tiles
+    # (csrc/nm_sdp_stream.hip) and the backward recomputes the weights from two floats per row
+    if ancestors is None and ops.sdp_stream_wanted(tq, tk, d // heads, backward=tape.recording):
+        return _sdp_attention_stream(tape, q, k, v, key_mask, heads, bq, tq, bk, tk, causal, keep_prob, salt, k_data,
+                                     v_data, w_out, out, k3, v3, step)
+    w = w_out if w_out is not None else (tape.buf((bq, heads, tq, tk)) if tape.recording else None)
     if ancestors is not None:            # a decoding step whose cache rows are addressed through an ancestor table
         assert tq == 1 and bq == bk and keep_prob >= 1.0 and not tape.recording
         ops.sdp_attn_step(q.data.view(bq, 1, d), k3, v3, key_mask, heads, ancestors, out.data.view(bq, 1, d), w)
@@ -841,6 +846,33 @@ def sdp_attention(tape: Tape, q: Var, k: Var, v: Var, key_mask: Optional[torch.T
         ops.sdp_attn_bwd(q.data.view(bq, tq, d), k3, v3, key_mask, w, out.grad.view(bq, tq, d), heads,
                          gq.view(bq, tq, d), gk.view(bk, tk, d), gv.view(bk, tk, d),
                          de, causal, keep_prob, salt, accumulate=aq, step=step)
+    tape.record(bwd)
+    return out
+
+
+def _sdp_attention_stream(tape, q, k, v, key_mask, heads, bq, tq, bk, tk, causal, keep_prob, salt, k_data, v_data,
+                          w_out, out, k3, v3, step):
+    """sdp_attention where the resident kernels refuse: no [bq, heads, tq, tk] buffer unless ``w_out`` asks for one."""
+    d = q.shape[1]
+    stats = tape.buf((2, bq, heads, tq)) if tape.recording else None
+    row_max, row_sum = (stats[0], stats[1]) if stats is not None else (None, None)
+    ops.sdp_stream_fwd(q.data.view(bq, tq, d), k3, v3, key_mask, heads, out.data.view(bq, tq, d), w_out, row_max,
+                       row_sum, causal, bq // bk, keep_prob, salt, step)
+
+    def bwd():
+        if out.grad is None:
+            return
+        assert bq == bk and k_data is None and v_data is None
+        ws = tape.buf((bq, heads, tq))
+        (gq, aq), (gk, ak), (gv, av) = tape.grad_slot(q), tape.grad_slot(k), tape.grad_slot(v)
+        if not (aq == ak == av):         # one accumulate flag for the three outputs: zero whichever buffer is fresh
+            for g, a in ((gq, aq), (gk, ak), (gv, av)):
+                if not a:
+                    ops.zero(g)
+            aq = True
+        ops.sdp_stream_bwd(q.data.view(bq, tq, d), k3, v3, key_mask, out.data.view(bq, tq, d), row_max, row_sum,
+                           out.grad.view(bq, tq, d), heads, gq.view(bq, tq, d), gk.view(bk, tk, d),
+                           gv.view(bk, tk, d), ws, causal, keep_prob, salt, accumulate=aq, step=step)
     tape.record(bwd)
     return out
 

@@ -17,12 +17,14 @@ ARCH = "gfx950"
 # v_pk_mul_f32, v_pk_fma_f32): its arithmetic is per-lane log-space sums that gain nothing from them.  nm_edit.hip gets
 # the same flag as a guard only: its arithmetic is integer, and its device assembly is the same with and without the
 # flag -- it keeps a later floating-point line in that file from bringing the packed forms in.  nm_chrf.hip likewise:
-# integer counts and a double-precision finish.  The host half of the compilation does not know the feature and says so
+# integer counts and a double-precision finish.  nm_sdp_stream.hip: its fp32 work is on the matrix cores and in per-lane
+# softmax scalars; the rescale of four accumulators by one scalar is the only place the packed forms could appear.  The host half of the compilation does not know the feature and says so
 # in a warning.
 SOURCE_FLAGS = {
     "nm_ctc_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "nm_edit.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "nm_chrf.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "nm_sdp_stream.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

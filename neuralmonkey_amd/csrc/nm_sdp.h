@@ -52,6 +52,19 @@ struct SdpBwdArgs {
     int accumulate;            // dq/dk/dv += instead of =
 };
 
+// LDS bytes of the resident kernels (nm_sdp_attention.hip): the key / value tiles of a head (forward) and the key /
+// value / query / gradient tiles (backward) stay in LDS whichever kernel runs.  Past NM_SDP_LDS_LIMIT nm_sdp_attn_fwd /
+// nm_sdp_attn_bwd refuse, and the streaming kernels (nm_sdp_stream.hip) are the ones that are wanted.
+#define NM_SDP_LDS_LIMIT (160 * 1024)
+static inline size_t sdp_fwd_lds(long Tk, long dh) { return sizeof(float) * (2 * Tk * (dh + 1) + Tk + 4 * dh + 4 * Tk); }
+static inline size_t sdp_bwd_lds(long Tq, long Tk, long dh) {
+    return sizeof(float) * (2 * (Tk + Tq) * (dh + 1) + Tk + 4 * Tk);
+}
+
+// Tq == 1 dispatch of the wave-per-(row, head) kernel (nm_sdp_attention.hip), which streams the keys from global
+// memory and has no LDS bound.  Returns false when the shape is not taken (odd head widths, unaligned operands).
+bool nm_sdp_decode_launch(const SdpArgs& p, const int* anc, long anc_ld, hipStream_t st);
+
 // Matrix-core paths (nm_sdp_mfma.hip).  Return true when the shape was taken (launch issued), false when the caller
 // has to fall back to the wave-per-query kernels.
 bool nm_sdp_mfma_fwd(const SdpArgs& p, hipStream_t stream);

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(1024) void sdp_decode_kernel(SdpArgs p, const int* 
 }
 
 // Tq == 1 dispatch.  Returns false when the shape is not taken (odd head widths, unaligned operands).
-static bool sdp_decode_launch(const SdpArgs& p, const int* anc, long anc_ld, hipStream_t st) {
+bool nm_sdp_decode_launch(const SdpArgs& p, const int* anc, long anc_ld, hipStream_t st) {
     if (p.Tq != 1 || p.dh % 4 || 64 % (p.dh / 4) || p.dh > 256) return false;
     const int d = p.H * p.dh;
     if (d % 4 || p.q_bs % 4 || p.k_bs % 4 || p.v_bs % 4 || p.ctx_bs % 4 || !nm_aligned16(p.q) || !nm_aligned16(p.k) ||
@@ -197,8 +197,6 @@ static bool sdp_decode_launch(const SdpArgs& p, const int* anc, long anc_ld, hip
     return true;
 }
 
-static size_t sdp_fwd_lds(long Tk, long dh) { return sizeof(float) * (2 * Tk * (dh + 1) + Tk + 4 * dh + 4 * Tk); }
-
 extern "C" int nm_sdp_attn_fwd(void* stream, const float* q, int64_t q_bs, const float* k, int64_t k_bs,
                                const float* v, int64_t v_bs, const float* key_mask, int64_t mask_bs, int64_t Bq,
                                int64_t rows_per_key, int64_t Tq, int64_t Tk, int64_t H, int64_t dh, int causal,
@@ -212,7 +210,7 @@ extern "C" int nm_sdp_attn_fwd(void* stream, const float* q, int64_t q_bs, const
     NM_REQUIRE(Bq * H < (1LL << 31), "nm_sdp_attn_fwd: grid too large");
     NM_REQUIRE(Bq * H * Tq * Tk < (1LL << 32) || keep_prob >= 1.0f, "nm_sdp_attn_fwd: dropout mask index overflow");
     const size_t lds = sdp_fwd_lds(Tk, dh);
-    NM_REQUIRE(lds <= 160 * 1024, "nm_sdp_attn_fwd: Tk=%ld x dh=%ld key/value tile does not fit LDS", (long)Tk,
+    NM_REQUIRE(lds <= NM_SDP_LDS_LIMIT, "nm_sdp_attn_fwd: Tk=%ld x dh=%ld key/value tile does not fit LDS", (long)Tk,
                (long)dh);
     SdpArgs p;
     p.q = q; p.q_bs = q_bs; p.k = k; p.k_bs = k_bs; p.v = v; p.v_bs = v_bs;
@@ -224,7 +222,7 @@ extern "C" int nm_sdp_attn_fwd(void* stream, const float* q, int64_t q_bs, const
     if (nm_sdp_mfma_fwd(p, nm_stream(stream))) {      // training / encoding shapes: matrix cores (nm_sdp_mfma.hip)
         NM_LAUNCH_CHECK("nm_sdp_attn_fwd (mfma)");
     }
-    if (nm_cur()->sw.sdp_decode && sdp_decode_launch(p, nullptr, 0, nm_stream(stream))) {     // one query per row
+    if (nm_cur()->sw.sdp_decode && nm_sdp_decode_launch(p, nullptr, 0, nm_stream(stream))) {     // one query per row
         NM_LAUNCH_CHECK("nm_sdp_attn_fwd (decode)");
     }
     static std::atomic<unsigned> attr_devs{0};                     // the attribute is per device: one bit per device id
@@ -254,7 +252,7 @@ extern "C" int nm_sdp_attn_step(void* stream, const float* q, int64_t q_bs, cons
     p.Bq = (int)Bq; p.rpk = 1; p.Tq = 1; p.Tk = (int)Tk; p.H = (int)H; p.dh = (int)dh; p.causal = 0;
     p.scale = 1.0f / sqrtf((float)dh);
     p.keep_prob = 1.0f; p.inv_keep = 1.0f; p.salt = 0; p.step = nullptr;
-    NM_REQUIRE(sdp_decode_launch(p, ancestors, anc_ld, nm_stream(stream)),
+    NM_REQUIRE(nm_sdp_decode_launch(p, ancestors, anc_ld, nm_stream(stream)),
                "nm_sdp_attn_step: dh=%ld must be 4, 8, 16, 32, 64, 128 or 256 and the operands 16-byte aligned",
                (long)dh);
     NM_LAUNCH_CHECK("nm_sdp_attn_step");
@@ -374,8 +372,8 @@ extern "C" int nm_sdp_attn_bwd(void* stream, const float* q, int64_t q_bs, const
     NM_REQUIRE(B > 0 && Tq > 0 && Tk > 0 && H > 0 && dh > 0, "nm_sdp_attn_bwd: bad shape");
     NM_REQUIRE(keep_prob > 0.0f && keep_prob <= 1.0f, "nm_sdp_attn_bwd: keep_prob %g outside (0,1]", keep_prob);
     NM_REQUIRE(B * H < (1LL << 31), "nm_sdp_attn_bwd: grid too large");
-    size_t lds = sizeof(float) * (2 * (Tk + Tq) * (dh + 1) + Tk + 4 * Tk);
-    NM_REQUIRE(lds <= 160 * 1024, "nm_sdp_attn_bwd: Tq=%ld Tk=%ld dh=%ld tiles do not fit LDS", (long)Tq, (long)Tk,
+    size_t lds = sdp_bwd_lds(Tq, Tk, dh);
+    NM_REQUIRE(lds <= NM_SDP_LDS_LIMIT, "nm_sdp_attn_bwd: Tq=%ld Tk=%ld dh=%ld tiles do not fit LDS", (long)Tq, (long)Tk,
                (long)dh);
     const size_t lds_w = lds + sizeof(float) * 2 * Tq * (Tk + 1);
     const bool wlds = lds_w <= 160 * 1024;          // base shape (T=50, dh=64): 72 KB

@@ -7,7 +7,9 @@ over time (:170-172).
 
 MI355X mapping: all B*S positions of a batch go through every dense layer as one MFMA GEMM, the
 attention core is one fused kernel launch per layer (``nm_sdp_attn_fwd``: K/V tiles of a head in
-LDS, wave-level softmax).  The layer stack is recorded on an autodiff tape; ``backward`` replays it.
+LDS, wave-level softmax; past 154 positions at head width 64, where those tiles no longer fit 160 KiB,
+``nm_sdp_stream_fwd`` / ``_bwd``: keys and values streamed through LDS in tiles of 64 with an online softmax, the
+weights recomputed in the backward pass -- ``autodiff.sdp_attention`` decides).  The layer stack is recorded on an autodiff tape; ``backward`` replays it.
 """
 from typing import List, Optional
 

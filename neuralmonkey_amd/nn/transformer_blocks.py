@@ -3,7 +3,8 @@
 attention/transformer_cross_layer.py:12-103) on the autodiff tape.
 
 Every dense layer is an MFMA GEMM over all B*T rows; the attention core is the fused
-``nm_sdp_attn_fwd`` kernel.  Variable names follow the TF scopes of the reference
+``nm_sdp_attn_fwd`` kernel or, for sequences past its LDS bound (training: 154 positions at head width 64, 78 at
+128), the streaming ``nm_sdp_stream_fwd`` / ``nm_sdp_stream_bwd`` kernels.  Variable names follow the TF scopes of the reference
 (``layer_<i>/self_attention/query_proj/kernel`` ...), so TF checkpoints map one to one."""
 import math
 import os

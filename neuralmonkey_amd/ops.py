@@ -1096,6 +1096,56 @@ def sdp_attn_bwd(q, k, v, key_mask, weights, dctx, heads, dq, dk, dv, de_ws, cau
                                    de_ws.data_ptr(), int(accumulate)), "nm_sdp_attn_bwd")
 
 
+# ---- attention past the LDS bound of the two above (include/nmhip_sdp_stream.h, csrc/nm_sdp_stream.hip) ----------------
+def sdp_stream_wanted(tq, tk, dh, backward=False):
+    """True where sdp_attn_fwd (and, with ``backward``, sdp_attn_bwd) refuses the shape for lack of LDS."""
+    return bool(_lib.load().nm_sdp_stream_wanted(tq, tk, dh, int(bool(backward))))
+
+
+def sdp_stream_workspace(bq, heads, tq, device):
+    """The backward's workspace: one float per (row, head, query)."""
+    n = _lib.load().nm_sdp_stream_workspace_bytes(bq, heads, tq) // 4
+    return torch.empty((n,), dtype=torch.float32, device=device)
+
+
+def sdp_stream_fwd(q, k, v, key_mask, heads, ctx, weights=None, row_max=None, row_sum=None, causal=False,
+                   rows_per_key=1, keep_prob=1.0, salt=0, step=None):
+    """sdp_attn_fwd's operands, keys and values streamed through LDS in tiles of 64.  row_max / row_sum [Bq, H, Tq]
+    (both or neither) are what sdp_stream_bwd recomputes the weights from."""
+    lib = _lib.load()
+    bq, tq, d = q.shape
+    bk, tk, _ = k.shape
+    assert d % heads == 0 and bq == bk * rows_per_key and v.shape[1] == tk
+    mask_bs = 0
+    if key_mask is not None:
+        assert key_mask.dim() == 2 and key_mask.stride(1) == 1 and key_mask.shape[1] >= tk
+        mask_bs = key_mask.stride(0)
+    if weights is not None:
+        assert weights.is_contiguous() and weights.numel() == bq * heads * tq * tk
+    for stat in (row_max, row_sum):
+        assert stat is None or (stat.is_contiguous() and stat.numel() == bq * heads * tq)
+    _lib.check(lib.nm_sdp_stream_fwd(_stream(), q.data_ptr(), _bs(q), k.data_ptr(), _bs(k), v.data_ptr(), _bs(v),
+                                     _p(key_mask), mask_bs, bq, rows_per_key, tq, tk, heads, d // heads, int(causal),
+                                     float(keep_prob), int(salt) & 0xFFFFFFFF, _p(step), ctx.data_ptr(), _bs(ctx),
+                                     _p(weights), _p(row_max), _p(row_sum)), "nm_sdp_stream_fwd")
+    return ctx
+
+
+def sdp_stream_bwd(q, k, v, key_mask, ctx, row_max, row_sum, dctx, heads, dq, dk, dv, workspace, causal=False,
+                   keep_prob=1.0, salt=0, accumulate=False, step=None, rows_per_key=1):
+    lib = _lib.load()
+    b, tq, d = q.shape
+    tk = k.shape[1]
+    mask_bs = 0 if key_mask is None else key_mask.stride(0)
+    assert workspace.numel() >= b * heads * tq and row_max.numel() == row_sum.numel() == b * heads * tq
+    _lib.check(lib.nm_sdp_stream_bwd(_stream(), q.data_ptr(), _bs(q), k.data_ptr(), _bs(k), v.data_ptr(), _bs(v),
+                                     _p(key_mask), mask_bs, ctx.data_ptr(), _bs(ctx), row_max.data_ptr(),
+                                     row_sum.data_ptr(), dctx.data_ptr(), _bs(dctx), b, rows_per_key, tq, tk, heads,
+                                     d // heads, int(causal), float(keep_prob), int(salt) & 0xFFFFFFFF, _p(step),
+                                     dq.data_ptr(), _bs(dq), dk.data_ptr(), _bs(dk), dv.data_ptr(), _bs(dv),
+                                     workspace.data_ptr(), int(accumulate)), "nm_sdp_stream_bwd")
+
+
 def add_position(x, signal, out, t0=0):
     """out[b,t,:] = x[b,t,:] + signal[t0+t,:]; x [B,T,D] contiguous, signal [Tmax,D]."""
     lib = _lib.load()
